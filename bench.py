@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/sec of the per-frame VO hot path (ORB extract + Hamming match + 5-frame BA) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One rank per GPU: started WITHOUT a launcher (no WORLD_SIZE in the environment) and --gpus N > 1, the script starts the N ranks
@@ -26,10 +26,6 @@ import json
 import os
 import re
 import sys
-
-# one HIP stream per sequence shard (+ one per shard for uploads): lift the runtime's default of 4 hardware queues
-# BEFORE HIP initialises
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import threading
 import time
 
@@ -85,9 +81,17 @@ def parse(argv=None):
     ap.add_argument("--frames", type=int, default=150,
                     help="frames of every shard's sequence (SURVEY.md 8d config 2: 150 frames rendered from a 2048 x 2048 texture; cycled)")
     ap.add_argument("--tex-size", type=int, default=2048, help="side of the world texture a sequence is rendered from")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the timed loop's outputs (the `parity` object)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the single-sequence and resident-window runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the side measurements: roofline and per-kernel durations, the secondary runs, "
+                         "the CPU baselines and the oracle check of the timed loop's outputs (off: the result line holds the "
+                         "headline figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop computed in its last step to DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all; see dump_outputs).  The timed loop then also copies every frame's descriptors to the host")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-parity", action="store_true",
+                    help="with --full: skip the oracle check of the timed loop's outputs (the `parity` object)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the single-sequence and resident-window runs")
     ap.add_argument("--cpu-frames", type=int, default=150)
     ap.add_argument("--cpu-threads", type=int, default=-1,
                     help="also time the oracle with this many host threads, one sequence shard each (-1 = all cores, 0 = skip)")
@@ -244,6 +248,7 @@ class Shard:
             self.ctx.map_upload(self.map, tp["map_pos"], tp["map_desc"])
             self.kf = mvo.synth.keyframe_problem(n=1000, seed=21 + shard_id, width=args.width, height=args.height, K=self.K)
         self.traj = []
+        self._last_window = None
         self._setup_native(ba_mode, pipeline)
 
     def _setup_native(self, ba_mode, pipeline):
@@ -301,6 +306,7 @@ class Shard:
     def run(self, n):
         """n frames: one call into the native loop (the GIL is released for its whole duration)."""
         out = np.zeros((n, 12))
+        self._last_window = None
         r = frame_loop_lib().frame_loop_run(self.loop, n, out.ctypes.data_as(C.c_void_p))
         if r != 0:
             raise RuntimeError("frame loop failed (%d): %s | %s" % (r, self.ctx.last_error(), self.ctx_ba.last_error()))
@@ -321,6 +327,18 @@ class Shard:
         if r != 0:
             raise RuntimeError("frame_loop_export_window failed (%d)" % r)
         return (poses[:fle[0]], pts[:fle[1]], ep[:fle[2]], el[:fle[2]], uv[:fle[2]]), (poses_now[:fle[0]], pts_now[:fle[1]])
+
+    def last_window(self):
+        """(k, export_window(k)) for the window the last frame solved.  Exported once per run: the export puts the window's objects
+        back to their initial state, so a second export would no longer see what the solve wrote back."""
+        if self._last_window is None:
+            k = (self.state().frame_no - 1) % len(self.pool)
+            self._last_window = (k, self.export_window(k))
+        return self._last_window
+
+    def capture(self, on):
+        """Keep the keypoints, descriptors and matches of every extraction from now on (captured_frame returns the last)."""
+        frame_loop_lib().frame_loop_capture(self.loop, 1 if on else 0)
 
     def captured_frame(self):
         """Keypoints, descriptors and matches of the last frame extracted while frame_loop_capture was on."""
@@ -649,6 +667,9 @@ def run_benchmark(args, env):
     fps_ = max(1, args.frames_per_step)
     nframes = args.steps * fps_          # frames per shard inside the timed region
     run_steps(shards, args.warmup * fps_)
+    if args.dump_outputs:
+        for s in shards:          # (the last frame's keypoints, descriptors and matches are among the dumped outputs)
+            s.capture(True)
     st_before = [s.state() for s in shards]
     shards[0].ctx.ba_launch_stats(reset=True)
     elapsed_local = timed_run(shards, nframes, barrier)
@@ -726,6 +747,46 @@ def contract_line(args, R):
             "dtype": "u8 (extract/match) + f64 (BA)", "data": "synthetic"}
 
 
+def dump_outputs(args, R, out_dir, limit=64 << 20):
+    """What the timed loop computed in its last step (`--frames-per-step` frames of every shard) as its caller receives it, one
+    DIR/<name>.npy per array:
+      trajectory   [ranks x shards, frames, 12] f64  the step's trajectory rows (x y z, then R column by column)
+    and, for the shards of this rank, their rows one shard after the other (<name>_per_shard: rows of each shard, f64):
+      ba_poses     [shards, F, 4, 4] f64  the poses the last frame's BA solve wrote back into the frames of its window
+      ba_points    [rows, 3] f64          the landmarks it wrote back into the window's MapPoint objects (f32 values)
+      keypoints    [rows, 7] f64          the last frame's keypoints: x y size angle response octave class_id
+      descriptors  [rows, 32] f32         their ORB descriptors, one byte per column
+      matches      [rows, 4] f64          its matches with the previous frame: queryIdx trainIdx imgIdx distance
+    Shards are taken in order while the files stay within `limit` bytes; shards_dumped.npy holds how many were."""
+    fps_ = max(1, args.frames_per_step)
+    traj = R["traj_all"][:, :, -fps_:, :]
+    out = {"trajectory": np.ascontiguousarray(traj.reshape(-1, fps_, 12), np.float64)}
+    used = out["trajectory"].nbytes + (64 << 10)          # (headroom: the .npy headers and the per-shard row counts)
+    taken = []
+    for s in R["shards"]:
+        a = {}
+        if args.ba_mode == "rebuild":
+            _, (_, (P, X)) = s.last_window()
+            a["ba_poses"], a["ba_points"] = P[None], X
+        _, kps, desc, m = s.captured_frame()
+        a["keypoints"] = np.stack([kps[f].astype(np.float64) for f in kps.dtype.names], axis=1)
+        a["descriptors"] = desc.astype(np.float32)
+        a["matches"] = np.stack([m[f].astype(np.float64) for f in m.dtype.names], axis=1)
+        size = sum(x.nbytes for x in a.values())
+        if used + size > limit:
+            break
+        used += size
+        taken.append(a)
+    for name in (taken[0] if taken else {}):
+        out[name] = np.concatenate([a[name] for a in taken])
+        if name != "ba_poses":
+            out[name + "_per_shard"] = np.array([len(a[name]) for a in taken], np.float64)
+    out["shards_dumped"] = np.array([len(taken)], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main(argv=None, env=None):
     args = parse(argv)
     if env is None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -737,11 +798,13 @@ def main(argv=None, env=None):
     s0 = shards[0]
     if world != args.gpus and rank == 0:
         print("[bench] --gpus %d but the launcher started %d rank(s): n_gpus reports the ranks that ran" % (args.gpus, world), file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, R, args.dump_outputs)
 
     result = None
-    if rank == 0 and getattr(env, "minimal_report", False):      # CPU stand-in environments (tests/): the contract fields only
+    if rank == 0 and (not args.full or getattr(env, "minimal_report", False)):
+        # (a plain run, and the CPU stand-in environments of tests/: the contract fields only)
         result = contract_line(args, R)
-        print(json.dumps(result))
     elif rank == 0:
         plan_wgs = int(s0.ctx_ba.ba_plan()["wgs"]) if args.ba_mode == "rebuild" else 0   # (workgroups of the last timed window of shard 0)
         trials = sum(a.ba_trials - b.ba_trials for a, b in zip(st_after, st_before))
@@ -1016,6 +1079,9 @@ def main(argv=None, env=None):
             "kernels": kern,
             "kernel_ms_per_frame": {k: round(v, 5) for k, v in sorted(per_kernel.items(), key=lambda kv: -kv[1])},
         }
+    if result is not None:
+        if args.dump_outputs:
+            result["dump_outputs"] = True     # (its timed loop also copied every frame's features to the host: not a timing run)
         print(json.dumps(result))
     for s in shards:
         s.close()
@@ -1044,9 +1110,8 @@ def parity_check(args, shards, nframes, max_windows=32):
         bad, cuts, n_checked = [], set(), 0
         fix = args.ba == "pose_only"
         for s in shards[:max_windows]:
-            k = (s.state().frame_no - 1) % len(s.pool)
             plan = s.ctx_ba.ba_plan()
-            (P0, X0, ep, el, uv), (P_now, X_now) = s.export_window(k)
+            k, ((P0, X0, ep, el, uv), (P_now, X_now)) = s.last_window()
             pb = s.pool[k]
             Po, Xo, sto, _ = O.bundle_adjustment_blocked(P0, X0, ep, el, uv, pb["focal"], pb["cx"], pb["cy"], plan=plan, fix_points=fix)
             row = np.asarray(s.traj[-1])

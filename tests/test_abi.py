@@ -1,6 +1,5 @@
 """The C-ABI library loads and exports every symbol include/mvo_hip.h declares (no compute, no GPU needed),
 and the product never routes through the oracle."""
-import ctypes
 import os
 import re
 import subprocess
@@ -15,7 +14,9 @@ def _declared():
 
 
 def test_header_symbols_are_exported(mvo):
-    lib = ctypes.CDLL(mvo.LIB_PATH)
+    # (through the package's loader: torch's HIP runtime must be in the process before the library pulls in the system one,
+    # or every GPU test after this one in the same session finds no device)
+    lib = mvo.load_library()
     names = _declared()
     assert len(names) >= 20
     for n in names:

@@ -106,3 +106,111 @@ def test_sequences_are_rendered_by_worker_processes_like_the_generator_itself():
     # the defaults are the contract's: 150 frames from a 2048 x 2048 texture
     d = bench.parse([])
     assert d.frames == 150 and d.tex_size == 2048 and d.width == 640 and d.height == 480
+
+
+class _StubCtx:
+    def ba_launch_stats(self, reset=False):
+        return dict(launches=1, windows=1, ms=1.0)
+
+    def ba_service_times(self):
+        return {}
+
+    def synchronize(self):
+        pass
+
+
+class _StubShard:
+    """What bench.run_benchmark / dump_outputs use of a shard, without a GPU."""
+
+    def __init__(self, sid, made):
+        self.id, self.traj, self.ctx, self.frame, self.capture_from = sid, [], _StubCtx(), 0, None
+        made.append(self)
+
+    def state(self):
+        import types
+        return types.SimpleNamespace(frame_no=self.frame)
+
+    def run(self, n):
+        for _ in range(n):
+            self.traj.append(np.full(12, 1000.0 * self.id + self.frame))
+            self.frame += 1
+
+    def capture(self, on):
+        self.capture_from = self.frame if on else None      # (the first frame whose features are kept)
+
+    def last_window(self):
+        return 0, (None, (np.full((5, 4, 4), float(self.id)), np.full((7, 3), float(self.id))))
+
+    def captured_frame(self):
+        import __graft_entry__ as graft
+        mvo = graft.load_package()
+        k = np.zeros(4 + self.id, mvo.KEYPOINT_DTYPE)
+        k["x"], k["octave"] = self.id, 2
+        return self.frame - 1, k, np.full((len(k), 32), 200 + self.id, np.uint8), np.zeros(2, mvo.DMATCH_DTYPE)
+
+    def close(self):
+        pass
+
+
+class _StubEnv:
+    device = "cpu"
+
+    def __init__(self):
+        self.made = []
+
+    def sync(self):
+        pass
+
+    def make_shard(self, sid, args, ba_mode, pipeline, **kw):
+        return _StubShard(sid, self.made)
+
+
+def test_plain_run_prints_the_headline_only_and_dumps_the_last_step(tmp_path, monkeypatch, capsys):
+    """Without --full the run is set-up, warm-up, the timed steps and the result line: no shard beyond the headline ones (the side
+    runs of --full make their own), the contract fields only.  --dump-outputs DIR: the last step's trajectory rows of every shard
+    and, shard by shard, the BA write-back and the last frame's features, all float32 / float64 .npy."""
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    env = _StubEnv()
+    out = tmp_path / "out"
+    r = bench.main(["--steps", "3", "--warmup", "1", "--streams", "3", "--frames-per-step", "2", "--dump-outputs", str(out)], env=env)
+    assert [s.id for s in env.made] == [0, 1, 2]
+    # the features of every timed frame are kept (capture on from the first timed frame: 1 warm-up step of 2 frames before it)
+    assert [s.capture_from for s in env.made] == [2, 2, 2]
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and set(r) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                          "scaling", "vs_baseline", "dtype", "data", "dump_outputs"}
+    assert r["dump_outputs"] is True                     # (the line of a run whose loop also copied features out says so)
+    assert r["steps"] == 3 and r["unit"] == "frames/s" and r["higher_is_better"] is True
+    assert abs(r["value"] - 3 * 6 / (r["ms_per_step"] * 3e-3)) < 1e-6 * r["value"]          # 3 shards x 3 steps x 2 frames
+    load = lambda n: np.load(str(out / (n + ".npy")))
+    assert all(load(f[:-4]).dtype in (np.float32, np.float64) for f in os.listdir(out))
+    traj = load("trajectory")
+    assert traj.shape == (3, 2, 12) and np.array_equal(traj[:, :, 0], [[1000.0 * s + f for f in (6, 7)] for s in range(3)])
+    assert load("shards_dumped")[0] == 3 and load("ba_poses").shape == (3, 5, 4, 4) and load("ba_points").shape == (21, 3)
+    assert load("keypoints").shape == (15, 7) and np.array_equal(load("keypoints_per_shard"), [4, 5, 6])
+    assert np.array_equal(load("keypoints")[-1], [2, 0, 0, 0, 0, 2, 0]) and load("descriptors")[-1, 0] == 202
+    assert load("matches").shape == (6, 4) and np.array_equal(load("matches_per_shard"), [2, 2, 2])
+    # without the option: no capture, no marker in the line
+    env = _StubEnv()
+    r = bench.main(["--steps", "2", "--warmup", "1", "--streams", "2"], env=env)
+    assert "dump_outputs" not in r and [s.capture_from for s in env.made] == [None, None]
+
+
+def test_dump_outputs_stays_within_its_limit():
+    """Shards are taken in order while the files fit: a limit that holds the first shard's arrays only dumps that shard."""
+    import tempfile
+    import bench
+    args = bench.parse(["--streams", "3", "--frames-per-step", "2"])
+    made = []
+    shards = [_StubShard(s, made) for s in range(3)]
+    for s in shards:
+        s.run(4)
+    R = dict(traj_all=np.stack([np.stack(s.traj) for s in shards])[None], shards=shards)
+    first = 5 * 16 * 8 + 7 * 3 * 8 + 4 * 7 * 8 + 4 * 32 * 4 + 2 * 4 * 8      # poses, points, keypoints, descriptors, matches
+    with tempfile.TemporaryDirectory() as d:
+        bench.dump_outputs(args, R, d, limit=3 * 2 * 12 * 8 + (64 << 10) + first)
+        assert np.load(os.path.join(d, "shards_dumped.npy"))[0] == 1
+        assert np.array_equal(np.load(os.path.join(d, "keypoints_per_shard.npy")), [4])
+        assert np.load(os.path.join(d, "trajectory.npy")).shape == (3, 2, 12)

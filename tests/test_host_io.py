@@ -5,7 +5,7 @@ import subprocess
 
 import numpy as np
 
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 
 BIN = os.path.join(ROOT, "monocular-visual-odometry_amd", "host", "tests", "test_io")
 
@@ -66,9 +66,9 @@ def test_config_and_trajectory_round_trip(tmp_path):
 
 
 def test_reference_config_parses_if_present(tmp_path):
-    ref = "/root/reference/config/config.yaml"
-    if not os.path.exists(ref):
-        return                                                   # the GPU box has no reference checkout
+    """tests/golden/reference_config.yaml: the reference project's config/config.yaml, unmodified (MIT License, Copyright (c) 2019
+    Feiyu Chen)."""
+    ref = os.path.join(GOLDEN, "reference_config.yaml")
     tin = tmp_path / "in.txt"
     tin.write_text("0 0 0 1 0 0 0 1 0 0 0 1\n")
     r = subprocess.run([BIN, ref, str(tin), str(tmp_path / "o.txt")], capture_output=True, text=True, timeout=60)

@@ -28,8 +28,8 @@ run_bounded() {
   return $rc
 }
 trim() { find $OUT -name "*_kernel_trace.csv" -delete; find $OUT -name "*_counter_collection.csv" -delete; find $OUT -name "*_agent_info.csv" -delete; }
-NOX="--no-cpu-baseline --no-secondary --no-parity"
-DRV="python bench.py --gpus 1 --steps 20 --warmup 5"
+NOX="--full --no-cpu-baseline --no-secondary --no-parity"
+DRV="python bench.py --gpus 1 --steps 20 --warmup 5 --full"
 ONE="python bench.py --steps 3 --warmup 1 --streams 1 --pipeline 0 $NOX"
 C4="python bench.py --width 1242 --height 375 --max-kp 4000 --ba-poses 10 --ba-points 4000 --streams 8 --steps 3 --warmup 1 $NOX"
 pmc() {  # pmc <name> <seconds> "<counters>" <command...>   -> $OUT/<name>.txt (per-kernel table)
@@ -93,7 +93,7 @@ pmc config4_pmc_mfma_busy 150 "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_
 trim
 }
 sec6() {
-run_bounded 600 $OUT/bench_default.err bash -c "python bench.py > $OUT/bench_default.json"
+run_bounded 600 $OUT/bench_default.err bash -c "python bench.py --full > $OUT/bench_default.json"
 }
 for sct in ${SECTIONS:-0 1 2 3 4 5 6}; do sec$sct; done
 trim

@@ -32,7 +32,7 @@ except Exception as e:
     print(sys.argv[2], "failed", e)
 PY
 }
-B="python bench.py --gpus 1 --steps 20 --warmup 5 --no-secondary --no-cpu-baseline $EXTRA"
+B="python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-secondary --no-cpu-baseline $EXTRA"
 for rep in $(seq 1 $REPS); do
   for v in "$@"; do
     label=${v%%:*}; envs=""
