@@ -293,6 +293,16 @@ int mvo_triangulate_points(mvo_ctx* ctx, const float* kp_prev, const float* kp_c
 int mvo_find_essential_inliers(mvo_ctx* ctx, const float* kp_prev, const float* kp_curr, int n, double fx, double fy,
                                double cx, double cy, double prob, double threshold, int32_t* inliers, int cap,
                                int* n_inliers);
+/* cv::findHomography(src, dst, cv::RANSAC, threshold, noArray(), 2000, confidence) as estiMotionByHomography calls
+ * it during the monocular initialisation (src/geometry/motion_estimation.cpp, reached from vo_addFrame.cpp:36-69;
+ * the reference passes threshold 3 and the default confidence 0.995).  src / dst: the matched pixels of the first
+ * keyframe and of the current frame (n x 2 float).  RANSAC over 4-point normalised DLT hypotheses (cv::RNG
+ * subsets with checkSubset, at most 2000 iterations, adaptive count), then for n > 4 the DLT on the inliers and
+ * 10 Levenberg-Marquardt iterations on the 8 free entries.  H: row-major 3 x 3 as findHomography returns it (not
+ * divided by H(2,2)); found = 0 when findHomography returns an empty matrix (n < 4, no subset passes checkSubset,
+ * no hypothesis with 4 inliers).  inliers: ascending indices of the RANSAC mask, capacity cap >= n. */
+int mvo_find_homography(mvo_ctx* ctx, const float* src, const float* dst, int n, double threshold, double confidence,
+                        double* H, int32_t* inliers, int cap, int* n_inliers, int* found);
 /* VisualOdometry::retainGoodTriangulationResult_ (src/vo/vo.cpp:181-244), host-side (acos + a sort for the
  * median): keep[i] lists the points whose triangulation angle (degrees) is >= min_triang_angle and at most
  * max_ratio_to_median times the median; angles (n, may be NULL) receives every angle. */
@@ -374,6 +384,12 @@ int mvo_debug_get_pnp(mvo_ctx* ctx, double* models, int32_t* counts, int cap, in
  * (iterations x 10 candidates, -1 = no such candidate), info[5] = {best iteration, best candidate, iterations
  * the sequential loop ran, iterations evaluated, 0}.  Returns the number of evaluated iterations. */
 int mvo_debug_get_essential(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32_t* info);
+
+/* Record of the last mvo_find_homography on this ctx: the inlier count of every evaluated hypothesis (-1 = runKernel
+ * found no model), info[6] = {selected iteration (-1: none), iterations the sequential loop ran, iterations
+ * evaluated, subsets drawn before getSubset gave up (2000 when it never did), LM iterations, DLT re-fit on the
+ * inliers used}.  Returns the number of evaluated iterations. */
+int mvo_debug_get_homography(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32_t* info);
 
 #ifdef __cplusplus
 }

@@ -438,6 +438,29 @@ class Context:
         return dict(counts=counts[:it].copy(), best_iter=int(info[0]), best_model=int(info[1]), iters_run=int(info[2]),
                     evaluated=int(info[3]))
 
+    def find_homography(self, src, dst, threshold=3.0, confidence=0.995):
+        """cv::findHomography(src, dst, RANSAC, threshold) of estiMotionByHomography -> dict(H (3 x 3, or None when
+        findHomography returns an empty matrix), inliers (ascending indices of the RANSAC mask))."""
+        a = np.ascontiguousarray(src, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(dst, np.float32).reshape(-1, 2)
+        assert len(a) == len(b)
+        n = len(a)
+        H = np.zeros(9)
+        inl = np.zeros(max(n, 1), np.int32)
+        cnt, found = C.c_int(), C.c_int()
+        self._chk(self.lib.mvo_find_homography(self.h, _p(a), _p(b), n, C.c_double(threshold), C.c_double(confidence),
+                                               _p(H), _p(inl), len(inl), C.byref(cnt), C.byref(found)))
+        return dict(H=H.reshape(3, 3) if found.value else None, inliers=inl[:cnt.value].copy())
+
+    def debug_homography(self):
+        counts = np.zeros(2000, np.int32)
+        info = np.zeros(6, np.int32)
+        it = self.lib.mvo_debug_get_homography(self.h, _p(counts), 2000, _p(info))
+        if it < 0:
+            self._chk(it)
+        return dict(counts=counts[:it].copy(), best_iter=int(info[0]), iters_run=int(info[1]), evaluated=int(info[2]),
+                    n_subsets=int(info[3]), lm_iters=int(info[4]), dlt=int(info[5]))
+
     def debug_pnp(self, cap=4096):
         models = np.zeros((cap, 12))
         counts = np.zeros(cap, np.int32)

@@ -277,6 +277,12 @@ int track_launch_em_hypotheses(mvo_ctx* ctx, const double* d_q1, const double* d
                                int n_hyp, float thr2, double* d_E, int32_t* d_nm, int32_t* d_counts);
 int track_launch_em_mask(mvo_ctx* ctx, const double* d_q1, const double* d_q2, int n, const double* d_E, float thr2,
                          uint8_t* d_mask);
+int track_launch_h_hypotheses(mvo_ctx* ctx, const float* d_src, const float* d_dst, int n, const int32_t* d_subsets,
+                              int n_hyp, float thr2, double* d_H, int32_t* d_counts);
+int track_launch_h_mask(mvo_ctx* ctx, const float* d_src, const float* d_dst, int n, const double* d_H, float thr2,
+                        uint8_t* d_mask);
+int track_launch_h_refine(mvo_ctx* ctx, const float* d_src, const float* d_dst, const uint8_t* d_mask, int n,
+                          const double* d_H, double* d_out);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

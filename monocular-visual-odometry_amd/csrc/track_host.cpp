@@ -42,6 +42,14 @@ struct mvo_track_state {
     double* d_em_E = nullptr;
     std::vector<int32_t> em_counts;  // record of the last call: [iterations evaluated x 10]
     int32_t em_info[5] = {-1, -1, 0, 0, 0};
+    // homography RANSAC
+    float* d_hpts = nullptr;  // src (2n) then dst (2n)
+    uint8_t* d_h_mask = nullptr;
+    int cap_h_pts = 0;
+    int32_t *d_h_subsets = nullptr, *d_h_counts = nullptr;
+    double *d_h_H = nullptr, *d_h_out = nullptr;
+    std::vector<int32_t> h_counts;  // record of the last call: [iterations evaluated]
+    int32_t h_info[6] = {-1, 0, 0, 0, 0, 0};
     // map points in view
     uint8_t* d_view_desc = nullptr;
     int32_t* d_view_n = nullptr;
@@ -176,6 +184,110 @@ bool invert_pose_lu(const double* T, double* out, int rows = 3) {
     return true;
 }
 
+// HomographyEstimatorCallback::checkSubset (OpenCV 4.x fundam.cpp) on the 4 drawn matches.  haveCollinearPoints
+// tests the triples that contain the LAST point of the subset (the loop of fundam.cpp: i = count - 1), in either
+// image; then the four triangle orientations must agree in both images for all four triangles or for none.
+bool h_collinear(const float* p, const int32_t* idx) {
+    const int i = 3;
+    for (int j = 0; j < i; ++j) {
+        const double dx1 = p[2 * idx[j]] - p[2 * idx[i]];
+        const double dy1 = p[2 * idx[j] + 1] - p[2 * idx[i] + 1];
+        for (int k = 0; k < j; ++k) {
+            const double dx2 = p[2 * idx[k]] - p[2 * idx[i]];
+            const double dy2 = p[2 * idx[k] + 1] - p[2 * idx[i] + 1];
+            if (std::fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (std::fabs(dx1) + std::fabs(dy1) + std::fabs(dx2) + std::fabs(dy2)))
+                return true;
+        }
+    }
+    return false;
+}
+
+double h_det3(const float* p, int a, int b, int c) {  // cv::determinant(Matx33d) of rows (x, y, 1)
+    const double m[9] = {p[2 * a], p[2 * a + 1], 1., p[2 * b], p[2 * b + 1], 1., p[2 * c], p[2 * c + 1], 1.};
+    return m[0] * (m[4] * m[8] - m[7] * m[5]) - m[1] * (m[3] * m[8] - m[6] * m[5]) + m[2] * (m[3] * m[7] - m[6] * m[4]);
+}
+
+bool h_check_subset(const float* src, const float* dst, const int32_t* idx) {
+    if (h_collinear(src, idx) || h_collinear(dst, idx)) return false;
+    static const int tt[4][3] = {{0, 1, 2}, {1, 2, 3}, {0, 2, 3}, {0, 1, 3}};
+    int negative = 0;
+    for (int i = 0; i < 4; ++i) {
+        const int* t = tt[i];
+        negative += h_det3(src, idx[t[0]], idx[t[1]], idx[t[2]]) * h_det3(dst, idx[t[0]], idx[t[1]], idx[t[2]]) < 0;
+    }
+    return negative == 0 || negative == 4;
+}
+
+// RANSACPointSetRegistrator::getSubset (maxAttempts 1000) for up to max_iters iterations of findHomography's loop.
+// Returns how many subsets were drawn before getSubset gave up (the loop breaks there; 0 = the call fails).
+int draw_h_subsets(const float* src, const float* dst, int count, int max_iters, int32_t* out) {
+    MwcRng rng;
+    for (int it = 0; it < max_iters; ++it) {
+        int32_t* s = out + 4 * it;
+        bool found = false;
+        for (int attempt = 0; attempt < 1000 && !found; ++attempt) {
+            for (int i = 0; i < 4; ++i) {
+                bool fresh;
+                do {
+                    s[i] = rng.uniform(0, count);
+                    fresh = true;
+                    for (int j = 0; j < i; ++j) fresh = fresh && s[j] != s[i];
+                } while (!fresh);
+            }
+            found = h_check_subset(src, dst, s);
+        }
+        if (!found) return it;
+    }
+    return max_iters;
+}
+
+// The sequential bookkeeping of RANSACPointSetRegistrator::run over device-evaluated hypotheses, shared by
+// findEssentialMat and findHomography.  The hypotheses [0, total) are launched in two chunks (chunk_end); after each
+// chunk the counts (per_hyp candidates per hypothesis, -1 = none) are read back and the loop is advanced until its own
+// adaptive stopping rule (RANSACUpdateNumIters, starting from niters) is met.  count == model_points: the first
+// model is the answer.  rec receives every evaluated count; info = {best hypothesis, best candidate, iterations the
+// sequential loop ran, hypotheses evaluated}.  The pinned staging may hold this call's uploads on entry.
+template <class Launch>
+int ransac_chunks(mvo_ctx* ctx, int n, int model_points, int total, int niters, int per_hyp, double prob,
+                  const int (&chunk_end)[2], const int32_t* d_counts, Launch&& launch, std::vector<int32_t>& rec,
+                  int32_t* info) {
+    int evaluated = 0, max_good = 0, it = 0, best_it = -1, best_m = -1, r;
+    bool first_wait = true;
+    for (int c = 0; c < 2 && it < niters; ++c) {
+        const int end = std::min(chunk_end[c], total);
+        if (end <= evaluated) continue;
+        if ((r = launch(evaluated, end))) return r;
+        if (first_wait) {  // the staging area still holds the uploads of this call
+            MVO_HIP(hipStreamSynchronize(ctx->stream));
+            first_wait = false;
+        }
+        int32_t* h_counts = reinterpret_cast<int32_t*>(ctx->h_pin);
+        MVO_HIP(hipMemcpyAsync(h_counts, d_counts + per_hyp * (size_t)evaluated, (size_t)(end - evaluated) * per_hyp * 4,
+                               hipMemcpyDeviceToHost, ctx->stream));
+        MVO_HIP(hipStreamSynchronize(ctx->stream));
+        rec.insert(rec.end(), h_counts, h_counts + (size_t)(end - evaluated) * per_hyp);
+        evaluated = end;
+        for (; it < niters && it < evaluated; ++it)
+            for (int m = 0; m < per_hyp; ++m) {
+                const int raw = rec[(size_t)it * per_hyp + m];
+                const int good = n == model_points && raw >= 0 ? n : raw;
+                if (good < 0) break;
+                if (good > std::max(max_good, model_points - 1)) {
+                    max_good = good;
+                    best_it = it;
+                    best_m = m;
+                    niters = update_num_iters(prob, (double)(n - good) / n, model_points, niters);
+                }
+                if (n == model_points) break;  // count == modelPoints: the first model is the answer
+            }
+    }
+    info[0] = best_it;
+    info[1] = best_m;
+    info[2] = it;
+    info[3] = evaluated;
+    return MVO_OK;
+}
+
 }  // namespace
 
 void track_release(mvo_ctx* ctx) {
@@ -197,6 +309,12 @@ void track_release(mvo_ctx* ctx) {
     free_dev(s->d_em_nm);
     free_dev(s->d_em_counts);
     free_dev(s->d_em_E);
+    free_dev(s->d_hpts);
+    free_dev(s->d_h_mask);
+    free_dev(s->d_h_subsets);
+    free_dev(s->d_h_counts);
+    free_dev(s->d_h_H);
+    free_dev(s->d_h_out);
     delete s;
     ctx->track = nullptr;
 }
@@ -555,45 +673,15 @@ int mvo_find_essential_inliers(mvo_ctx* ctx, const float* kp_prev, const float* 
     const float thr2 = (float)(thr * thr);
     const double* d_q1 = s->d_emq;
     const double* d_q2 = s->d_emq + 2 * (size_t)n;
-    // The hypotheses are evaluated in growing chunks; after each chunk the sequential bookkeeping of
-    // RANSACPointSetRegistrator::run is advanced over the new counts until the loop's own stopping rule is met.
-    const int chunk_end[2] = {256, kMaxIters};  // a chunk costs ~0.25 ms whatever its size (one wave per hypothesis)
-    int evaluated = 0, niters = total, max_good = 0, it = 0, best_it = -1, best_m = -1;
-    bool first_wait = true;
-    for (int c = 0; c < 2 && it < niters; ++c) {
-        const int end = std::min(chunk_end[c], total);
-        if (end <= evaluated) continue;
-        if ((r = track_launch_em_hypotheses(ctx, d_q1, d_q2, n, s->d_em_subsets + 5 * (size_t)evaluated, end - evaluated, thr2,
-                                            s->d_em_E + 90 * (size_t)evaluated, s->d_em_nm + evaluated,
-                                            s->d_em_counts + 10 * (size_t)evaluated)))
-            return r;
-        if (first_wait) {  // the staging area still holds the uploads of this call
-            MVO_HIP(hipStreamSynchronize(ctx->stream));
-            first_wait = false;
-        }
-        int32_t* h_counts = reinterpret_cast<int32_t*>(ctx->h_pin);
-        MVO_HIP(hipMemcpyAsync(h_counts, s->d_em_counts + 10 * (size_t)evaluated, (size_t)(end - evaluated) * 40,
-                               hipMemcpyDeviceToHost, ctx->stream));
-        MVO_HIP(hipStreamSynchronize(ctx->stream));
-        s->em_counts.insert(s->em_counts.end(), h_counts, h_counts + (size_t)(end - evaluated) * 10);
-        evaluated = end;
-        for (; it < niters && it < evaluated; ++it)
-            for (int m = 0; m < 10; ++m) {
-                const int good = n == kModel && s->em_counts[(size_t)it * 10 + m] >= 0 ? n : s->em_counts[(size_t)it * 10 + m];
-                if (good < 0) break;
-                if (good > std::max(max_good, kModel - 1)) {
-                    max_good = good;
-                    best_it = it;
-                    best_m = m;
-                    niters = update_num_iters(prob, (double)(n - good) / n, kModel, niters);
-                }
-                if (n == kModel) break;  // count == modelPoints: the first model is the answer
-            }
-    }
-    s->em_info[0] = best_it;
-    s->em_info[1] = best_m;
-    s->em_info[2] = it;
-    s->em_info[3] = evaluated;
+    // The hypotheses are evaluated in growing chunks (a chunk costs ~0.25 ms whatever its size: one wave per hypothesis)
+    const int chunk_end[2] = {256, kMaxIters};
+    auto launch = [&](int begin, int end) {
+        return track_launch_em_hypotheses(ctx, d_q1, d_q2, n, s->d_em_subsets + 5 * (size_t)begin, end - begin, thr2,
+                                          s->d_em_E + 90 * (size_t)begin, s->d_em_nm + begin, s->d_em_counts + 10 * (size_t)begin);
+    };
+    if ((r = ransac_chunks(ctx, n, kModel, total, total, 10, prob, chunk_end, s->d_em_counts, launch, s->em_counts, s->em_info)))
+        return r;
+    const int best_it = s->em_info[0], best_m = s->em_info[1];
     if (best_it < 0) {
         if (ctx->prof) mvo_prof_collect(ctx);
         return MVO_OK;
@@ -622,6 +710,115 @@ int mvo_debug_get_essential(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32_
     if (info) std::memcpy(info, s->em_info, sizeof(s->em_info));
     if (iters > cap_iters) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_debug_get_essential: buffer too small", hipSuccess);
     if (counts && iters) std::memcpy(counts, s->em_counts.data(), s->em_counts.size() * 4);
+    return iters;
+}
+
+// ---------------------------------------------------------------------------------------------- initialisation
+// cv::findHomography(src, dst, RANSAC, threshold, noArray(), maxIters 2000, confidence) as estiMotionByHomography
+// calls it: n < 4 -> no model; n == 4 -> runKernel on the four matches, all inliers; otherwise the RANSAC loop
+// (getSubset with checkSubset, one wave per hypothesis on the device) and, when it found a model, the DLT re-fit on
+// its inliers followed by the Levenberg-Marquardt refinement (k_h_refine).  The mask stays RANSAC's mask.
+int mvo_find_homography(mvo_ctx* ctx, const float* src, const float* dst, int n, double threshold, double confidence,
+                        double* H, int32_t* inliers, int cap, int* n_inliers, int* found) {
+    if (!ctx || n < 0 || !H || !n_inliers || !found || cap < 0 || (n && (!src || !dst)) || (cap && !inliers))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "bad arguments", hipSuccess);
+    if (!(confidence > 0 && confidence < 1))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_find_homography: confidence must be in (0, 1)", hipSuccess);
+    *n_inliers = 0;
+    *found = 0;
+    for (int k = 0; k < 9; ++k) H[k] = 0;
+    mvo_track_state* s = state(ctx);
+    s->h_counts.clear();
+    s->h_info[0] = -1;
+    for (int k = 1; k < 6; ++k) s->h_info[k] = 0;
+    constexpr int kModel = 4, kMaxIters = 2000;
+    if (n < kModel) return MVO_OK;
+    if (cap < n) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_find_homography: inlier buffer smaller than n", hipSuccess);
+    if (threshold <= 0) threshold = 3;  // findHomography's defaultRANSACReprojThreshold
+    MVO_HIP(hipSetDevice(ctx->device));
+    if (n > s->cap_h_pts) {
+        free_dev(s->d_hpts);
+        free_dev(s->d_h_mask);
+        s->cap_h_pts = 0;
+        const int c = std::max(4096, n + n / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_hpts, (size_t)c * 4 * sizeof(float)));
+        MVO_HIP(hipMalloc((void**)&s->d_h_mask, (size_t)c));
+        s->cap_h_pts = c;
+    }
+    if (!s->d_h_subsets) {
+        MVO_HIP(hipMalloc((void**)&s->d_h_subsets, (size_t)kMaxIters * 4 * sizeof(int32_t)));
+        MVO_HIP(hipMalloc((void**)&s->d_h_counts, (size_t)kMaxIters * sizeof(int32_t)));
+        MVO_HIP(hipMalloc((void**)&s->d_h_H, (size_t)kMaxIters * 9 * sizeof(double)));
+        MVO_HIP(hipMalloc((void**)&s->d_h_out, 16 * sizeof(double)));
+    }
+    const size_t bp = (size_t)n * 16, bs = (size_t)kMaxIters * 4 * sizeof(int32_t);
+    int r = mvo_ensure_pinned(ctx, std::max(bp + bs, (size_t)kMaxIters * 4 + (size_t)n + 256));
+    if (r) return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(ctx->h_pin, src, (size_t)n * 8);
+    std::memcpy(ctx->h_pin + (size_t)n * 8, dst, (size_t)n * 8);
+    int32_t* subsets = reinterpret_cast<int32_t*>(ctx->h_pin + bp);
+    int total = 1;
+    if (n == kModel)
+        for (int i = 0; i < kModel; ++i) subsets[i] = i;
+    else
+        total = draw_h_subsets(src, dst, n, kMaxIters, subsets);
+    s->h_info[3] = total;
+    if (total == 0) return MVO_OK;  // getSubset gave up at the first iteration: findHomography fails
+    MVO_HIP(hipMemcpyAsync(s->d_hpts, ctx->h_pin, bp, hipMemcpyHostToDevice, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(s->d_h_subsets, subsets, (size_t)total * 4 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    const float* d_src = s->d_hpts;
+    const float* d_dst = s->d_hpts + 2 * (size_t)n;
+    const float thr2 = (float)(threshold * threshold);
+    const int chunk_end[2] = {256, kMaxIters};
+    auto launch = [&](int begin, int end) {
+        return track_launch_h_hypotheses(ctx, d_src, d_dst, n, s->d_h_subsets + 4 * (size_t)begin, end - begin, thr2,
+                                         s->d_h_H + 9 * (size_t)begin, s->d_h_counts + begin);
+    };
+    int32_t info[4];
+    if ((r = ransac_chunks(ctx, n, kModel, total, n == kModel ? 1 : kMaxIters, 1, confidence, chunk_end, s->d_h_counts,
+                           launch, s->h_counts, info)))
+        return r;
+    const int best = info[0];
+    s->h_info[0] = best;
+    s->h_info[1] = info[2];
+    s->h_info[2] = info[3];
+    if (best < 0) {
+        if (ctx->prof) mvo_prof_collect(ctx);
+        return MVO_OK;
+    }
+    double* h_out = reinterpret_cast<double*>(ctx->h_pin);
+    uint8_t* h_mask = ctx->h_pin + 128;
+    int cnt = 0;
+    if (n == kModel) {
+        MVO_HIP(hipMemcpyAsync(h_out, s->d_h_H + 9 * (size_t)best, 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        MVO_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < n; ++i) inliers[cnt++] = i;
+    } else {
+        if ((r = track_launch_h_mask(ctx, d_src, d_dst, n, s->d_h_H + 9 * (size_t)best, thr2, s->d_h_mask))) return r;
+        if ((r = track_launch_h_refine(ctx, d_src, d_dst, s->d_h_mask, n, s->d_h_H + 9 * (size_t)best, s->d_h_out))) return r;
+        MVO_HIP(hipMemcpyAsync(h_out, s->d_h_out, 11 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        MVO_HIP(hipMemcpyAsync(h_mask, s->d_h_mask, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        MVO_HIP(hipStreamSynchronize(ctx->stream));
+        for (int i = 0; i < n; ++i)
+            if (h_mask[i]) inliers[cnt++] = i;
+        s->h_info[4] = (int32_t)h_out[9];
+        s->h_info[5] = (int32_t)h_out[10];
+    }
+    for (int k = 0; k < 9; ++k) H[k] = h_out[k];
+    if (ctx->prof) mvo_prof_collect(ctx);
+    *n_inliers = cnt;
+    *found = 1;
+    return MVO_OK;
+}
+
+int mvo_debug_get_homography(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32_t* info) {
+    if (!ctx || !ctx->track) return mvo_set_err(ctx, MVO_ERR_STATE, "no homography call on this ctx yet", hipSuccess);
+    const mvo_track_state* s = ctx->track;
+    const int iters = (int)s->h_counts.size();
+    if (info) std::memcpy(info, s->h_info, sizeof(s->h_info));
+    if (iters > cap_iters) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_debug_get_homography: buffer too small", hipSuccess);
+    if (counts && iters) std::memcpy(counts, s->h_counts.data(), (size_t)iters * 4);
     return iters;
 }
 

@@ -7,6 +7,9 @@
 //   k_triangulate      geometry::helperTriangulatePoints (motion_estimation.cpp:214-247) on a keyframe's matches.
 //   k_em_hypotheses    the RANSAC loop of cv::findEssentialMat (epipolar_geometry.cpp:36-39): one wave per five-point
 //   k_em_mask          hypothesis; the inlier mask of the selected candidate.
+//   k_h_hypotheses     the RANSAC loop of cv::findHomography (estiMotionByHomography, monocular initialisation): one
+//   k_h_mask           wave per 4-point DLT hypothesis; the inlier mask of the selected one;
+//   k_h_refine         the DLT on all inliers + LMSolver (10 iterations) that findHomography runs after RANSAC.
 // The arithmetic lives in pnp_wave.h (wave-level SPMD code); this file binds it to threads and LDS.
 #include "mvo_internal.h"
 
@@ -18,6 +21,7 @@
 #define PW_SYNC() __syncthreads()
 #define PW_UNROLL _Pragma("unroll")
 #include "em_wave.h"
+#include "h_wave.h"
 
 // ------------------------------------------------------------------------------------------------ map in view
 // One workgroup walks the map in chunks of 1024 points and appends the survivors in map order (the reference
@@ -273,6 +277,78 @@ int track_launch_pnp_refine(mvo_ctx* ctx, const float* d_p3, const float* d_p2, 
     ProfScope ps(ctx, "k_pnp_refine");
     hipLaunchKernelGGL(k_pnp_refine, dim3(1), dim3(pw::kRefLanes), 0, ctx->stream, d_p3, d_p2, d_masks, n, cam, d_models,
                        d_counts, n_hyp, confidence, forced_best, mode, d_Mg, d_mg, d_best_mask, d_out);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ homography
+// cv::findHomography's RANSAC loop: one wave per hypothesis runs HomographyEstimatorCallback::runKernel on its 4
+// matches and counts the inliers over all n (-1: degenerate subset, runKernel returned no model).
+__global__ __launch_bounds__(pw::kHLanes) void k_h_hypotheses(const float* __restrict__ src, const float* __restrict__ dst,
+                                                             int n, const int32_t* __restrict__ subsets, float thr2,
+                                                             double* __restrict__ H, int32_t* __restrict__ counts) {
+    __shared__ pw::HDltLds lds;
+    const size_t h = blockIdx.x;
+    double Hh[9];
+    const bool ok = pw::h_hypothesis(lds, src, dst, subsets + 4 * h, Hh);
+    const int good = ok ? pw::h_count(lds, src, dst, n, Hh, thr2) : -1;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) H[9 * h + k] = ok ? Hh[k] : 0.0;
+        counts[h] = good;
+    }
+}
+
+// inlier mask of the selected hypothesis (the bestMask of RANSACPointSetRegistrator::run)
+__global__ __launch_bounds__(256) void k_h_mask(const float* __restrict__ src, const float* __restrict__ dst, int n,
+                                                const double* __restrict__ H, float thr2, uint8_t* __restrict__ mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float Hf[9];
+    for (int k = 0; k < 9; ++k) Hf[k] = (float)H[k];
+    mask[i] = pw::h_error(Hf, src[2 * i], src[2 * i + 1], dst[2 * i], dst[2 * i + 1]) <= thr2 ? 1 : 0;
+}
+
+// findHomography after RANSAC (n > 4): runKernel on the inliers (kept when it yields a model), then the LM on the
+// 8 free entries.  out: H[9], then (double) LM iterations, DLT re-fit used.
+__global__ __launch_bounds__(pw::kHLanes) void k_h_refine(const float* __restrict__ src, const float* __restrict__ dst,
+                                                         const uint8_t* __restrict__ mask, int n,
+                                                         const double* __restrict__ H_ransac, double* __restrict__ out) {
+    __shared__ pw::HRefLds lds;
+    double H[9], Hn[9];
+    for (int k = 0; k < 9; ++k) H[k] = H_ransac[k];
+    const bool dlt = pw::h_dlt_inliers(lds, src, dst, mask, n, Hn);
+    if (dlt)
+        for (int k = 0; k < 9; ++k) H[k] = Hn[k];
+    const int iters = pw::h_refine_lm(lds, src, dst, mask, n, H);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 9; ++k) out[k] = H[k];
+        out[9] = iters;
+        out[10] = dlt ? 1 : 0;
+    }
+}
+
+int track_launch_h_hypotheses(mvo_ctx* ctx, const float* d_src, const float* d_dst, int n, const int32_t* d_subsets,
+                              int n_hyp, float thr2, double* d_H, int32_t* d_counts) {
+    ProfScope ps(ctx, "k_h_hypotheses");
+    hipLaunchKernelGGL(k_h_hypotheses, dim3(n_hyp), dim3(pw::kHLanes), 0, ctx->stream, d_src, d_dst, n, d_subsets, thr2,
+                       d_H, d_counts);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+int track_launch_h_mask(mvo_ctx* ctx, const float* d_src, const float* d_dst, int n, const double* d_H, float thr2,
+                        uint8_t* d_mask) {
+    ProfScope ps(ctx, "k_h_mask");
+    hipLaunchKernelGGL(k_h_mask, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_src, d_dst, n, d_H, thr2, d_mask);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+int track_launch_h_refine(mvo_ctx* ctx, const float* d_src, const float* d_dst, const uint8_t* d_mask, int n,
+                          const double* d_H, double* d_out) {
+    ProfScope ps(ctx, "k_h_refine");
+    hipLaunchKernelGGL(k_h_refine, dim3(1), dim3(pw::kHLanes), 0, ctx->stream, d_src, d_dst, d_mask, n, d_H, d_out);
     MVO_HIP(hipGetLastError());
     return MVO_OK;
 }

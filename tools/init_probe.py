@@ -1,0 +1,59 @@
+"""Wall time of mvo_find_homography (host clock around the synchronous call, warmed up, >= 50 repeats) at 500 / 1000 / 2000
+matches with 0 / 50 % wrong matches, beside the sequential CPU restatement of the same call (tests/homography_restatement.cpp).
+Per-kernel device times: run it under rocprofv3 --kernel-trace --stats.
+Usage: python tools/init_probe.py [--reps 50] [--out FILE]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import __graft_entry__ as graft  # noqa: E402
+import h_restate as HR  # noqa: E402
+
+
+def timed(fn, reps):
+    fn()
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts) * 1e3), float(np.min(ts) * 1e3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    mvo = graft.load_package()
+    ctx = mvo.Context(0)
+    R = HR.Restatement()
+    rows = []
+    for n in (500, 1000, 2000):
+        for frac in (0.0, 0.5):
+            pr = HR.two_view(n, 100 + n, planar=True, noise=0.5, outlier_frac=frac)
+            s, d = pr["src"], pr["dst"]
+            ctx.find_homography(s, d)
+            dbg = ctx.debug_homography()
+            gpu_med, gpu_min = timed(lambda: ctx.find_homography(s, d), a.reps)
+            cpu_med, cpu_min = timed(lambda: R.find_homography(s, d), max(5, a.reps // 10))
+            rows.append(dict(n=n, outliers=frac, iters_run=dbg["iters_run"], evaluated=dbg["evaluated"],
+                             lm_iters=dbg["lm_iters"], gpu_ms_median=gpu_med, gpu_ms_min=gpu_min,
+                             cpu_restatement_ms_median=cpu_med))
+            print(json.dumps(rows[-1]), flush=True)
+    ctx.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
