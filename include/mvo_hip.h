@@ -87,7 +87,11 @@ int mvo_orb_configure(mvo_ctx* ctx, const mvo_orb_params* params);
 /* geometry::calcKeyPoints (src/geometry/feature_match.cpp:11-36; called from Frame::calcKeyPoints,
  * include/my_slam/vo/frame.h:73-76): cv::ORB::detect + selectUniformKptsByGrid.  image: u8, `channels`
  * = 1 (gray) or 3/4 (BGR[A] as cv::imread gives, run_vo.cpp:114).  The device pyramid built here stays
- * cached in the ctx for mvo_calc_descriptors(reuse_pyramid=1). */
+ * cached in the ctx for mvo_calc_descriptors(reuse_pyramid=1).
+ * Input limits (deviation 6): every pyramid level must be at least 8 px in each
+ * direction (cvRound(width / scale_factor^(nlevels-1)) >= 8, same for height) and width at most 8192 px;
+ * otherwise MVO_ERR_INVALID.  cv::ORB has neither limit: it returns no keypoints from a level under
+ * 63 px (so none at all from a frame that small) and the keypoints of the larger levels otherwise. */
 int mvo_calc_keypoints(mvo_ctx* ctx, const uint8_t* image, int width, int height, int stride,
                        int channels, mvo_keypoint* kps, int cap, int* n);
 /* Same with the image already resident in HBM (bench: inputs resident when the timed region starts). */

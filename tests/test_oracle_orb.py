@@ -156,23 +156,49 @@ def test_harris_and_angle_on_analytic_patterns(O):
 
 
 def test_fast_atan2_polynomial_accuracy(O):
-    # IC angle of a linear ramp I = ax + by + c is atan2(b, a) up to the 0.3 deg polynomial error
+    """cv::fastAtan2's 7th-order polynomial is within 0.01 deg of float64 atan2 (its published error is 0.0096 deg).  The
+    oracle's angles are first tied bit for bit to tests/orb_numpy.fast_atan2 of their own integer moments, then that
+    polynomial is held to atan2 over every integer moment pair in [-700, 700]^2, the axes, the octant boundaries and large
+    moments (the disc's moments reach 10^6)."""
+    import orb_numpy as N
+    from conftest import graft
+    img = graft.load_package().synth.small_test_image(12, 200, 150, channels=1)
+    p = P(O, nlevels=1, fast_threshold=10)
+    cand = O.candidates(img, p)
+    assert len(cand) > 50
+    m10, m01 = N.moments(N.with_frame(img), cand["x"].astype(np.int64), cand["y"].astype(np.int64))
+    got = N.fast_atan2(m01.astype(np.float32), m10.astype(np.float32))
+    assert got.view(np.uint32).tolist() == cand["angle"].view(np.uint32).tolist()
+
+    def err(y, x):
+        a = N.fast_atan2(y.astype(np.float32), x.astype(np.float32)).astype(np.float64)
+        assert ((a >= 0) & (a <= 360)).all()
+        return np.abs((a - np.degrees(np.arctan2(y, x)) + 180) % 360 - 180)
+    y, x = np.mgrid[-700:701, -700:701]
+    dense = err(y.astype(np.float64).ravel(), x.astype(np.float64).ravel())
+    assert dense.max() < 0.01 and dense.max() > 0.009, dense.max()                 # the bound is tight, not loose
+    t = np.concatenate([np.arange(1, 2001), np.geomspace(2000, 2e6, 200).astype(np.int64)]).astype(np.float64)
+    z = np.zeros_like(t)
+    for yy, xx in ((z, t), (t, z), (z, -t), (-t, z), (t, t), (t, -t), (-t, t), (-t, -t), (t + 1, t), (t, t + 1), (-t - 1, t)):
+        e = err(yy, xx)
+        assert e.max() < 0.01, e.max()
+    assert err(np.array([0.0, 0.0, 5.0, -5.0]), np.array([1.0, -1.0, 0.0, 0.0])).max() == 0   # exact on the axes
+    rng = np.random.RandomState(0)
+    big = rng.randint(-2_000_000, 2_000_001, (2, 200000)).astype(np.float64)
+    assert err(big[0], big[1]).max() < 0.01
+    # the IC angle of a linear ramp (a bright FAST centre on it) is the ramp's direction and atan2 of the patch's moments
     ys, xs = np.mgrid[0:101, 0:101]
     for ang in (10, 45, 100, 180, 225, 300, 359):
         a, b = np.cos(np.deg2rad(ang)), np.sin(np.deg2rad(ang))
-        ramp = 128 + 2.0 * (a * (xs - 50) + b * (ys - 50))
-        img = np.clip(np.rint(ramp), 0, 255).astype(np.uint8)
-        img2, c = _fast_img(9, 0, center=255, ring=0, base=0)
-        mask = np.zeros_like(img2, bool)
-        mask[c, c] = True
-        for k in range(9):
-            pass
-        patch = np.where(img2 != 0, img2, img)
-        cand = O.candidates(patch, P(O, nlevels=1, fast_threshold=10))
-        hit = cand[(cand["x"] == c) & (cand["y"] == c)]
-        if len(hit):
-            d = abs((hit[0]["angle"] - ang + 180) % 360 - 180)
-            assert d < 8.0, (ang, hit[0]["angle"])
+        ramp = np.clip(np.rint(128 + 2.0 * (a * (xs - 50) + b * (ys - 50))), 0, 255).astype(np.uint8)
+        ramp[50, 50] = 255
+        cand = O.candidates(ramp, P(O, nlevels=1, fast_threshold=10))
+        hit = cand[(cand["x"] == 50) & (cand["y"] == 50)]
+        assert len(hit) == 1, ang
+        m10, m01 = N.moments(N.with_frame(ramp), np.array([50]), np.array([50]))
+        exact = np.degrees(np.arctan2(float(m01[0]), float(m10[0])))
+        assert abs((hit[0]["angle"] - exact + 180) % 360 - 180) < 0.01, (ang, hit[0]["angle"], exact)
+        assert abs((hit[0]["angle"] - ang + 180) % 360 - 180) < 1.0, (ang, hit[0]["angle"])
 
 
 def test_grid_sampling_rules(O):
