@@ -307,6 +307,31 @@ int mvo_find_essential_inliers(mvo_ctx* ctx, const float* kp_prev, const float* 
  * no hypothesis with 4 inliers).  inliers: ascending indices of the RANSAC mask, capacity cap >= n. */
 int mvo_find_homography(mvo_ctx* ctx, const float* src, const float* dst, int n, double threshold, double confidence,
                         double* H, int32_t* inliers, int cap, int* n_inliers, int* found);
+/* estiMotionByEssential (src/geometry/epipolar_geometry.cpp:17-57), the essential-matrix branch of the monocular
+ * initialisation (called at src/geometry/motion_estimation.cpp:44-50): findEssentialMat(pts1, pts2, focal, pp,
+ * RANSAC, prob, threshold) exactly as mvo_find_essential_inliers runs it (the reference passes prob 0.999 and threshold
+ * 1.0, config/config.yaml:101-102), E /= E(2,2), then recoverPose(E, pts1, pts2, R, t, focal, pp, mask) with
+ * focal = (fx + fy) / 2, pp = the cv::Point2f (cx, cy) and distanceThresh 50, then t /= sqrt(t1^2 + t2^2 + t0^2).
+ * Both divisions by a scalar multiply by its reciprocal (cv::Mat::convertTo).  E, R: row-major 3 x 3; t: 3.
+ * inliers: ascending indices of the RANSAC mask (taken before recoverPose), capacity cap >= n.  found = 0 when
+ * n < 5, when RANSAC finds no model, and when n == 5 and the five-point solver returns several candidates (the
+ * reference's decomposeEssentialMat asserts on the stacked 3k x 3 matrix; DESIGN.md section 2, deviation 7).
+ * Rotation-only scenes are not special-cased: E, R and t are whatever the decomposition of the fitted E gives. */
+int mvo_esti_motion_by_essential(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy,
+                                 double cx, double cy, double prob, double threshold, double* E, double* R, double* t,
+                                 int32_t* inliers, int cap, int* n_inliers, int* found);
+/* checkEssentialScore and checkHomographyScore (src/geometry/motion_estimation.cpp:501-664, sigma 1 by default,
+ * include/my_slam/geometry/motion_estimation.h:104,110; called at motion_estimation.cpp:135-138).  E: as
+ * mvo_esti_motion_by_essential returns it; H: mvo_find_homography's H times 1 / H(2,2); K = [fx 0 cx; 0 fy cy; 0 0 1].
+ * inl_e / inl_h: the lists to score (indices into pts1 / pts2).  Either model may be NULL: its score is then 0 and
+ * its kept list empty.  score_*: the sums in the declared block order of DESIGN.md section 12 (NaN for a match on
+ * the epipole, as the reference's loop gives); kept_*: the entries that passed both terms, in list order, capacity
+ * n_e / n_h.  The reference leaves checkHomographyScore's sum uninitialised; it starts from 0.0 here (DESIGN.md
+ * section 2, deviation 8). */
+int mvo_check_init_scores(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy, double cx,
+                          double cy, const double* E, const int32_t* inl_e, int n_e, const double* H,
+                          const int32_t* inl_h, int n_h, double sigma, double* score_e, double* score_h, int32_t* kept_e,
+                          int* n_kept_e, int32_t* kept_h, int* n_kept_h);
 /* VisualOdometry::retainGoodTriangulationResult_ (src/vo/vo.cpp:181-244), host-side (acos + a sort for the
  * median): keep[i] lists the points whose triangulation angle (degrees) is >= min_triang_angle and at most
  * max_ratio_to_median times the median; angles (n, may be NULL) receives every angle. */
@@ -394,6 +419,12 @@ int mvo_debug_get_essential(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32_
  * evaluated, subsets drawn before getSubset gave up (2000 when it never did), LM iterations, DLT re-fit on the
  * inliers used}.  Returns the number of evaluated iterations. */
 int mvo_debug_get_homography(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32_t* info);
+
+/* Record of the last mvo_esti_motion_by_essential on this ctx (zeros and chosen = -1 when it found no model):
+ * good[4] = recoverPose's counts for (R1, t), (R2, t), (R1, -t), (R2, -t); chosen = the index picked (0..3);
+ * R1R2t = R1 (9), R2 (9), t (3) of decomposeEssentialMat; masks[i] bit k set when match i passes combination k
+ * and the RANSAC mask.  Returns n (the number of masks). */
+int mvo_debug_get_recover_pose(mvo_ctx* ctx, int32_t* good, int32_t* chosen, double* R1R2t, uint8_t* masks, int cap);
 
 #ifdef __cplusplus
 }

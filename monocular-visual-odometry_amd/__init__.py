@@ -452,6 +452,54 @@ class Context:
                                                _p(H), _p(inl), len(inl), C.byref(cnt), C.byref(found)))
         return dict(H=H.reshape(3, 3) if found.value else None, inliers=inl[:cnt.value].copy())
 
+    def esti_motion_by_essential(self, kp1, kp2, K, prob=0.999, threshold=1.0):
+        """estiMotionByEssential -> dict(found, E (scaled by 1 / E(2,2)), R, t (unit), inliers (ascending indices of
+        the RANSAC mask)); E, R, t are None when found is False."""
+        a = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
+        assert len(a) == len(b)
+        n = len(a)
+        E, R, t = np.zeros(9), np.zeros(9), np.zeros(3)
+        inl = np.zeros(max(n, 1), np.int32)
+        cnt, found = C.c_int(), C.c_int()
+        self._chk(self.lib.mvo_esti_motion_by_essential(
+            self.h, _p(a), _p(b), n, C.c_double(K["fx"]), C.c_double(K["fy"]), C.c_double(K["cx"]), C.c_double(K["cy"]),
+            C.c_double(prob), C.c_double(threshold), _p(E), _p(R), _p(t), _p(inl), len(inl), C.byref(cnt), C.byref(found)))
+        ok = bool(found.value)
+        return dict(found=ok, E=E.reshape(3, 3) if ok else None, R=R.reshape(3, 3) if ok else None, t=t if ok else None,
+                    inliers=inl[:cnt.value].copy())
+
+    def debug_recover_pose(self, cap=1 << 16):
+        """Record of the last esti_motion_by_essential: dict(good (4 counts), chosen (0..3, -1: none), R1, R2, t of the
+        decomposition, masks (bit k: the match passes combination k))."""
+        good = np.zeros(4, np.int32)
+        chosen = C.c_int32()
+        d = np.zeros(21)
+        masks = np.zeros(cap, np.uint8)
+        n = self.lib.mvo_debug_get_recover_pose(self.h, _p(good), C.byref(chosen), _p(d), _p(masks), cap)
+        if n < 0:
+            self._chk(n)
+        return dict(good=good, chosen=int(chosen.value), R1=d[:9].reshape(3, 3), R2=d[9:18].reshape(3, 3), t=d[18:].copy(),
+                    masks=masks[:n].copy())
+
+    def check_init_scores(self, kp1, kp2, K, E, inl_e, H, inl_h, sigma=1.0):
+        """checkEssentialScore + checkHomographyScore -> dict(score_e, score_h, kept_e, kept_h).  E / H may be None."""
+        a = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
+        assert len(a) == len(b)
+        Ed = None if E is None else np.ascontiguousarray(E, np.float64).reshape(9)
+        Hd = None if H is None else np.ascontiguousarray(H, np.float64).reshape(9)
+        le = np.ascontiguousarray(inl_e if inl_e is not None else [], np.int32).reshape(-1)
+        lh = np.ascontiguousarray(inl_h if inl_h is not None else [], np.int32).reshape(-1)
+        ke, kh = np.zeros(max(len(le), 1), np.int32), np.zeros(max(len(lh), 1), np.int32)
+        se, sh = C.c_double(), C.c_double()
+        ne, nh = C.c_int(), C.c_int()
+        self._chk(self.lib.mvo_check_init_scores(
+            self.h, _p(a), _p(b), len(a), C.c_double(K["fx"]), C.c_double(K["fy"]), C.c_double(K["cx"]),
+            C.c_double(K["cy"]), _p(Ed), _p(le), len(le), _p(Hd), _p(lh), len(lh), C.c_double(sigma), C.byref(se),
+            C.byref(sh), _p(ke), C.byref(ne), _p(kh), C.byref(nh)))
+        return dict(score_e=se.value, score_h=sh.value, kept_e=ke[:ne.value].copy(), kept_h=kh[:nh.value].copy())
+
     def debug_homography(self):
         counts = np.zeros(2000, np.int32)
         info = np.zeros(6, np.int32)

@@ -534,5 +534,195 @@ PW_FN void score_essentials(EmLds& s, const double* q1, const double* q2, int n,
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// recoverPose(E, pts1, pts2, R, t, focal, pp, mask) after findEssentialMat, as estiMotionByEssential calls it
+// (src/geometry/epipolar_geometry.cpp:36-57).  Uniform code: every lane that needs the decomposition computes it.
+// Declared arithmetic:
+//   scaling       E /= E(2,2) and t /= |t| are cv::Mat::convertTo with alpha = 1 / s: every entry times (1.0 / s)
+//   decomposition svd3 (the canonical Jacobi, svd_small<3, 3>) of the scaled E; U and Vt negated when their 3 x 3
+//                 determinant (cv::determinant's cofactor expansion along row 0) is < 0; R1 = (U W) Vt,
+//                 R2 = (U W^T) Vt, each product entry summed k = 0..2 in order; t = U.col(2)
+//   cheirality   cvTriangulatePoints' 4 x 4 system with P0 = [I|0], rows x P(2,:) - P(0,:), y P(2,:) - P(1,:) per
+//                 view, the right singular vector of the smallest singular value of svd_small<4, 4> kept in double;
+//                 Q2 Q3 > 0, Q0..3 /= Q3, Q2 < dist, (P Q)(2) = ((P20 Q0 + P21 Q1) + P22 Q2) + P23 Q3 > 0 and < dist.
+// The null vector is unit length and its sign is the SVD's choice; a sign flip cancels exactly in Q2 Q3 and in every
+// quotient Qk / Q3 (IEEE negation is exact), so the sign convention cannot change a mask bit or a count.
+constexpr double kRpDistanceThresh = 50.0;
+
+PW_FN void rp_scale9(const double* M, double s, double (&out)[9]) {
+    const double a = 1.0 / s;
+    PW_UNROLL
+    for (int k = 0; k < 9; k++) out[k] = M[k] * a;
+}
+
+PW_FN double rp_det3(const double (&m)[3][3]) {
+    return m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+}
+
+PW_FN void rp_mul3(const double (&A)[3][3], const double (&B)[3][3], double (&C)[3][3]) {
+    PW_UNROLL
+    for (int i = 0; i < 3; i++) {
+        PW_UNROLL
+        for (int j = 0; j < 3; j++) {
+            double s = A[i][0] * B[0][j];
+            s = s + A[i][1] * B[1][j];
+            C[i][j] = s + A[i][2] * B[2][j];
+        }
+    }
+}
+
+// decomposeEssentialMat: R1R2t = R1 (9, row-major), R2 (9), t (3)
+PW_FN void decompose_essential(const double (&E)[9], double (&R1R2t)[21]) {
+    double A[3][3], U[3][3], W[3], V[3][3], Vt[3][3];
+    PW_UNROLL
+    for (int k = 0; k < 9; k++) A[k / 3][k % 3] = E[k];
+    svd3(A, U, W, V);
+    PW_UNROLL
+    for (int i = 0; i < 3; i++) {
+        PW_UNROLL
+        for (int j = 0; j < 3; j++) Vt[i][j] = V[j][i];
+    }
+    if (rp_det3(U) < 0) {
+        PW_UNROLL
+        for (int k = 0; k < 9; k++) U[k / 3][k % 3] = -U[k / 3][k % 3];
+    }
+    if (rp_det3(Vt) < 0) {
+        PW_UNROLL
+        for (int k = 0; k < 9; k++) Vt[k / 3][k % 3] = -Vt[k / 3][k % 3];
+    }
+    const double Wm[3][3] = {{0, 1, 0}, {-1, 0, 0}, {0, 0, 1}};
+    const double Wmt[3][3] = {{0, -1, 0}, {1, 0, 0}, {0, 0, 1}};
+    double UW[3][3], R[3][3];
+    rp_mul3(U, Wm, UW);
+    rp_mul3(UW, Vt, R);
+    PW_UNROLL
+    for (int k = 0; k < 9; k++) R1R2t[k] = R[k / 3][k % 3];
+    rp_mul3(U, Wmt, UW);
+    rp_mul3(UW, Vt, R);
+    PW_UNROLL
+    for (int k = 0; k < 9; k++) R1R2t[9 + k] = R[k / 3][k % 3];
+    PW_UNROLL
+    for (int r = 0; r < 3; r++) R1R2t[18 + r] = U[r][2];
+}
+
+// P = [R | t] of combination c (0: R1 t, 1: R2 t, 2: R1 -t, 3: R2 -t)
+PW_FN void rp_combination(const double (&R1R2t)[21], int c, double (&P)[12]) {
+    const double* R = R1R2t + ((c & 1) ? 9 : 0);
+    PW_UNROLL
+    for (int r = 0; r < 3; r++) {
+        PW_UNROLL
+        for (int k = 0; k < 3; k++) P[4 * r + k] = R[3 * r + k];
+        P[4 * r + 3] = c < 2 ? R1R2t[18 + r] : -R1R2t[18 + r];
+    }
+}
+
+// recoverPose's cheirality test of one match (normalised points) for the camera pair [I|0], P
+PW_FN bool rp_cheirality(double x1, double y1, double x2, double y2, const double (&P)[12], double dist) {
+    const double P0[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    double At[4][4], Vt[4][4], W[4];
+    PW_UNROLL
+    for (int k = 0; k < 4; k++) {
+        At[k][0] = x1 * P0[8 + k] - P0[k];
+        At[k][1] = y1 * P0[8 + k] - P0[4 + k];
+        At[k][2] = x2 * P[8 + k] - P[k];
+        At[k][3] = y2 * P[8 + k] - P[4 + k];
+    }
+    svd_small<4, 4>(At, Vt, W);
+    double Q0 = Vt[3][0], Q1 = Vt[3][1], Q2 = Vt[3][2], Q3 = Vt[3][3];
+    bool ok = Q2 * Q3 > 0;
+    Q0 = Q0 / Q3;
+    Q1 = Q1 / Q3;
+    Q2 = Q2 / Q3;
+    Q3 = Q3 / Q3;
+    ok = Q2 < dist && ok;
+    double z = P[8] * Q0 + P[9] * Q1;
+    z = z + P[10] * Q2;
+    z = z + P[11] * Q3;
+    ok = z > 0 && ok;
+    ok = z < dist && ok;
+    return ok;
+}
+
+// OpenCV's choice among the four counts: the first of 1, 2, 3, 4 that is >= all others
+PW_FN int rp_choose(const int32_t* good) {
+    if (good[0] >= good[1] && good[0] >= good[2] && good[0] >= good[3]) return 0;
+    if (good[1] >= good[0] && good[1] >= good[2] && good[1] >= good[3]) return 1;
+    if (good[2] >= good[0] && good[2] >= good[1] && good[2] >= good[3]) return 2;
+    return 3;
+}
+
+// R (9) and the normalised t (3) of the chosen combination; t / sqrt(t1^2 + t2^2 + t0^2) as epipolar_geometry.cpp:55-56
+PW_FN void rp_finish(const double (&R1R2t)[21], int chosen, double (&R)[9], double (&t)[3]) {
+    const double* Rs = R1R2t + ((chosen & 1) ? 9 : 0);
+    PW_UNROLL
+    for (int k = 0; k < 9; k++) R[k] = Rs[k];
+    PW_UNROLL
+    for (int r = 0; r < 3; r++) t[r] = chosen < 2 ? R1R2t[18 + r] : -R1R2t[18 + r];
+    double s = t[1] * t[1] + t[2] * t[2];
+    s = s + t[0] * t[0];
+    s = sqrt(s);
+    const double a = 1.0 / s;
+    PW_UNROLL
+    for (int r = 0; r < 3; r++) t[r] = t[r] * a;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The two terms of one listed match in checkEssentialScore / checkHomographyScore (motion_estimation.cpp:501-664),
+// in the reference's expression order; chi > th (NaN is not) drops a term and clears good.  f: F21, h: H21,
+// hi: H12 (row-major).
+PW_FN void score_e_terms(const double* f, double u1, double v1, double u2, double v2, double inv_s2, double* t1,
+                         double* t2, bool* good) {
+    const double th = 3.841, th_score = 5.991;
+    *good = true;
+    const double a2 = (f[0] * u1 + f[1] * v1) + f[2];
+    const double b2 = (f[3] * u1 + f[4] * v1) + f[5];
+    const double c2 = (f[6] * u1 + f[7] * v1) + f[8];
+    const double num2 = (a2 * u2 + b2 * v2) + c2;
+    const double sq1 = num2 * num2 / (a2 * a2 + b2 * b2);
+    const double chi1 = sq1 * inv_s2;
+    if (chi1 > th) {
+        *t1 = 0;
+        *good = false;
+    } else {
+        *t1 = th_score - chi1;
+    }
+    const double a1 = (f[0] * u2 + f[3] * v2) + f[6];
+    const double b1 = (f[1] * u2 + f[4] * v2) + f[7];
+    const double c1 = (f[2] * u2 + f[5] * v2) + f[8];
+    const double num1 = (a1 * u1 + b1 * v1) + c1;
+    const double sq2 = num1 * num1 / (a1 * a1 + b1 * b1);
+    const double chi2 = sq2 * inv_s2;
+    if (chi2 > th) {
+        *t2 = 0;
+        *good = false;
+    } else {
+        *t2 = th_score - chi2;
+    }
+}
+
+// checkHomographyScore adds nothing for a dropped term (t = 0 and add = false)
+PW_FN void score_h_terms(const double* h, const double* hi, double u1, double v1, double u2, double v2, double inv_s2,
+                         double* t1, bool* add1, double* t2, bool* add2, bool* good) {
+    const double th = 5.991;
+    *good = true;
+    const double w2in1inv = 1.0 / ((hi[6] * u2 + hi[7] * v2) + hi[8]);
+    const double u2in1 = ((hi[0] * u2 + hi[1] * v2) + hi[2]) * w2in1inv;
+    const double v2in1 = ((hi[3] * u2 + hi[4] * v2) + hi[5]) * w2in1inv;
+    const double sq1 = (u1 - u2in1) * (u1 - u2in1) + (v1 - v2in1) * (v1 - v2in1);
+    const double chi1 = sq1 * inv_s2;
+    *add1 = !(chi1 > th);
+    *t1 = *add1 ? th - chi1 : 0;
+    *good = *add1;
+    const double w1in2inv = 1.0 / ((h[6] * u1 + h[7] * v1) + h[8]);
+    const double u1in2 = ((h[0] * u1 + h[1] * v1) + h[2]) * w1in2inv;
+    const double v1in2 = ((h[3] * u1 + h[4] * v1) + h[5]) * w1in2inv;
+    const double sq2 = (u2 - u1in2) * (u2 - u1in2) + (v2 - v1in2) * (v2 - v1in2);
+    const double chi2 = sq2 * inv_s2;
+    *add2 = !(chi2 > th);
+    *t2 = *add2 ? th - chi2 : 0;
+    *good = *good && *add2;
+}
+
 }  // namespace pw
 #endif

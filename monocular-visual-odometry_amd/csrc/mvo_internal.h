@@ -135,6 +135,11 @@ inline size_t orb_detect_host_bytes(int n_tiles) {
 struct TrackCamera {
     double fx, fy, cx, cy;
 };
+struct InitScoreArgs {  // k_init_scores: F21, H21, H12 (row-major), 1 / sigma^2, which models exist
+    double f[9], h[9], hi[9];
+    double inv_s2;
+    int has_e, has_h;
+};
 struct TrackViewArgs {
     double T[12];  // rows 0..2 of T_c_w = inv(T_w_c)
     double fx, fy, cx, cy;
@@ -283,6 +288,10 @@ int track_launch_h_mask(mvo_ctx* ctx, const float* d_src, const float* d_dst, in
                         uint8_t* d_mask);
 int track_launch_h_refine(mvo_ctx* ctx, const float* d_src, const float* d_dst, const uint8_t* d_mask, int n,
                           const double* d_H, double* d_out);
+int track_launch_recover_pose(mvo_ctx* ctx, const double* d_q1, const double* d_q2, int n, const double* d_E,
+                              const uint8_t* d_ransac_mask, uint8_t* d_masks, int32_t* d_cnt, double* d_out);
+int track_launch_init_scores(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, const int32_t* d_lists, int n_e,
+                             int n_h, const InitScoreArgs& a, double* d_scores, int32_t* d_kept, int32_t* d_n_kept);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -50,6 +50,22 @@ struct mvo_track_state {
     double *d_h_H = nullptr, *d_h_out = nullptr;
     std::vector<int32_t> h_counts;  // record of the last call: [iterations evaluated]
     int32_t h_info[6] = {-1, 0, 0, 0, 0, 0};
+    // recoverPose after the essential-matrix RANSAC (record of the last call: mvo_debug_get_recover_pose)
+    uint8_t* d_rp_masks = nullptr;
+    int cap_rp = 0;
+    double* d_rp_out = nullptr;
+    int32_t* d_rp_cnt = nullptr;
+    int32_t rp_good[4] = {0, 0, 0, 0};
+    int32_t rp_chosen = -1;
+    double rp_R1R2t[21] = {};
+    std::vector<uint8_t> rp_masks;
+    int rp_n = 0;
+    // E / H scores
+    uint8_t* d_sc_in = nullptr;  // pts1 (2n float), pts2 (2n float), the E list, the H list
+    size_t cap_sc = 0;
+    int32_t* d_sc_kept = nullptr;
+    size_t cap_sc_kept = 0;
+    uint8_t* d_sc_out = nullptr;  // 2 scores, 2 kept counts
     // map points in view
     uint8_t* d_view_desc = nullptr;
     int32_t* d_view_n = nullptr;
@@ -288,6 +304,112 @@ int ransac_chunks(mvo_ctx* ctx, int n, int model_points, int total, int niters, 
     return MVO_OK;
 }
 
+// findEssentialMat(pts1, pts2, focal, pp, RANSAC, prob, threshold) on the device, shared by
+// mvo_find_essential_inliers and mvo_esti_motion_by_essential.  Leaves the normalised points in d_emq, every
+// hypothesis's candidates in d_em_E, the record in em_counts / em_info and, for n > 5 with a model, the RANSAC mask of
+// the selected candidate in d_em_mask (launched, not yet read back).  n < 5: no model.
+void reset_em_record(mvo_track_state* s) {
+    s->em_counts.clear();
+    s->em_info[0] = s->em_info[1] = -1;
+    s->em_info[2] = s->em_info[3] = s->em_info[4] = 0;
+}
+
+int essential_ransac(mvo_ctx* ctx, const float* kp_prev, const float* kp_curr, int n, double fx, double fy, double cx,
+                     double cy, double prob, double threshold) {
+    mvo_track_state* s = state(ctx);
+    reset_em_record(s);
+    constexpr int kModel = 5, kMaxIters = 1000;  // createRANSACPointSetRegistrator(cb, 5, threshold, prob) -> maxIters 1000
+    if (n < kModel) return MVO_OK;
+    MVO_HIP(hipSetDevice(ctx->device));
+    if (n > s->cap_em) {
+        free_dev(s->d_emq);
+        free_dev(s->d_em_mask);
+        s->cap_em = 0;
+        const int c = std::max(4096, n + n / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_emq, (size_t)c * 4 * sizeof(double)));
+        MVO_HIP(hipMalloc((void**)&s->d_em_mask, (size_t)c));
+        s->cap_em = c;
+    }
+    if (!s->d_em_subsets) {
+        MVO_HIP(hipMalloc((void**)&s->d_em_subsets, (size_t)kMaxIters * 5 * sizeof(int32_t)));
+        MVO_HIP(hipMalloc((void**)&s->d_em_nm, (size_t)kMaxIters * sizeof(int32_t)));
+        MVO_HIP(hipMalloc((void**)&s->d_em_counts, (size_t)kMaxIters * 10 * sizeof(int32_t)));
+        MVO_HIP(hipMalloc((void**)&s->d_em_E, (size_t)kMaxIters * 90 * sizeof(double)));
+    }
+    // findEssentialMat(points1, points2, focal, pp, ...): K = [focal 0 pp.x; 0 focal pp.y], pp a cv::Point2f built from
+    // K(0,2), K(1,2) (epipolar_geometry.cpp:27-28); points to double, (p - c) / f; threshold /= (fx + fy) / 2
+    const double focal = (fx + fy) / 2;
+    const double pcx = (double)(float)cx, pcy = (double)(float)cy;
+    const size_t bq = (size_t)n * 4 * sizeof(double), bs = (size_t)kMaxIters * 5 * sizeof(int32_t);
+    int r = mvo_ensure_pinned(ctx, std::max(bq + bs, (size_t)kMaxIters * 40 + 2 * (size_t)n + 512));
+    if (r) return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    double* q = reinterpret_cast<double*>(ctx->h_pin);
+    for (int i = 0; i < n; ++i) {
+        q[2 * i] = ((double)kp_prev[2 * i] - pcx) / focal;
+        q[2 * i + 1] = ((double)kp_prev[2 * i + 1] - pcy) / focal;
+        q[2 * (size_t)n + 2 * i] = ((double)kp_curr[2 * i] - pcx) / focal;
+        q[2 * (size_t)n + 2 * i + 1] = ((double)kp_curr[2 * i + 1] - pcy) / focal;
+    }
+    int32_t* subsets = reinterpret_cast<int32_t*>(ctx->h_pin + bq);
+    const int total = n == kModel ? 1 : kMaxIters;
+    if (n == kModel)
+        for (int i = 0; i < kModel; ++i) subsets[i] = i;
+    else
+        draw_subsets(n, kMaxIters, subsets);
+    MVO_HIP(hipMemcpyAsync(s->d_emq, q, bq, hipMemcpyHostToDevice, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(s->d_em_subsets, subsets, (size_t)total * 5 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    const double thr = threshold / ((focal + focal) / 2);
+    const float thr2 = (float)(thr * thr);
+    const double* d_q1 = s->d_emq;
+    const double* d_q2 = s->d_emq + 2 * (size_t)n;
+    // The hypotheses are evaluated in growing chunks (a chunk costs ~0.25 ms whatever its size: one wave per hypothesis)
+    const int chunk_end[2] = {256, kMaxIters};
+    auto launch = [&](int begin, int end) {
+        return track_launch_em_hypotheses(ctx, d_q1, d_q2, n, s->d_em_subsets + 5 * (size_t)begin, end - begin, thr2,
+                                          s->d_em_E + 90 * (size_t)begin, s->d_em_nm + begin, s->d_em_counts + 10 * (size_t)begin);
+    };
+    if ((r = ransac_chunks(ctx, n, kModel, total, total, 10, prob, chunk_end, s->d_em_counts, launch, s->em_counts, s->em_info)))
+        return r;
+    const int best_it = s->em_info[0], best_m = s->em_info[1];
+    if (best_it >= 0 && n != kModel)
+        return track_launch_em_mask(ctx, d_q1, d_q2, n, s->d_em_E + 90 * (size_t)best_it + 9 * (size_t)best_m, thr2,
+                                    s->d_em_mask);
+    return MVO_OK;
+}
+
+// cv::invert(DECOMP_LU) of a 3 x 3 double matrix: for n <= 3 OpenCV takes the closed form, the adjugate times
+// 1 / det3 (all zeros when det3 == 0), not the LU of larger matrices (invert_pose_lu).
+void invert3(const double* M, double* out) {
+    auto m = [&](int r, int c) { return M[3 * r + c]; };
+    double d = m(0, 0) * (m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1)) - m(0, 1) * (m(1, 0) * m(2, 2) - m(1, 2) * m(2, 0)) +
+               m(0, 2) * (m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0));
+    if (d == 0.) {
+        for (int k = 0; k < 9; ++k) out[k] = 0;
+        return;
+    }
+    d = 1. / d;
+    out[0] = (m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1)) * d;
+    out[1] = (m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2)) * d;
+    out[2] = (m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1)) * d;
+    out[3] = (m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2)) * d;
+    out[4] = (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) * d;
+    out[5] = (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) * d;
+    out[6] = (m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0)) * d;
+    out[7] = (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) * d;
+    out[8] = (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) * d;
+}
+
+// C = A B (3 x 3, row-major), each entry summed k = 0..2 in order
+void mul3(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double v = A[3 * i] * B[j];
+            v = v + A[3 * i + 1] * B[3 + j];
+            C[3 * i + j] = v + A[3 * i + 2] * B[6 + j];
+        }
+}
+
 }  // namespace
 
 void track_release(mvo_ctx* ctx) {
@@ -315,6 +437,12 @@ void track_release(mvo_ctx* ctx) {
     free_dev(s->d_h_counts);
     free_dev(s->d_h_H);
     free_dev(s->d_h_out);
+    free_dev(s->d_rp_masks);
+    free_dev(s->d_rp_out);
+    free_dev(s->d_rp_cnt);
+    free_dev(s->d_sc_in);
+    free_dev(s->d_sc_kept);
+    free_dev(s->d_sc_out);
     delete s;
     ctx->track = nullptr;
 }
@@ -623,76 +751,20 @@ int mvo_find_essential_inliers(mvo_ctx* ctx, const float* kp_prev, const float* 
     if (!(prob > 0 && prob < 1))
         return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_find_essential_inliers: prob must be in (0, 1)", hipSuccess);
     *n_inliers = 0;
-    mvo_track_state* s = state(ctx);
-    s->em_counts.clear();
-    s->em_info[0] = s->em_info[1] = -1;
-    s->em_info[2] = s->em_info[3] = s->em_info[4] = 0;
-    constexpr int kModel = 5, kMaxIters = 1000;  // createRANSACPointSetRegistrator(cb, 5, threshold, prob) -> maxIters 1000
-    if (n < kModel) return MVO_OK;
-    if (cap < n) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_find_essential_inliers: inlier buffer smaller than n", hipSuccess);
-    MVO_HIP(hipSetDevice(ctx->device));
-    if (n > s->cap_em) {
-        free_dev(s->d_emq);
-        free_dev(s->d_em_mask);
-        s->cap_em = 0;
-        const int c = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_emq, (size_t)c * 4 * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_mask, (size_t)c));
-        s->cap_em = c;
-    }
-    if (!s->d_em_subsets) {
-        MVO_HIP(hipMalloc((void**)&s->d_em_subsets, (size_t)kMaxIters * 5 * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_nm, (size_t)kMaxIters * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_counts, (size_t)kMaxIters * 10 * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_E, (size_t)kMaxIters * 90 * sizeof(double)));
-    }
-    // findEssentialMat(points1, points2, focal, pp, ...): K = [focal 0 pp.x; 0 focal pp.y], pp a cv::Point2f built from
-    // K(0,2), K(1,2) (epipolar_geometry.cpp:27-28); points to double, (p - c) / f; threshold /= (fx + fy) / 2
-    const double focal = (fx + fy) / 2;
-    const double pcx = (double)(float)cx, pcy = (double)(float)cy;
-    const size_t bq = (size_t)n * 4 * sizeof(double), bs = (size_t)kMaxIters * 5 * sizeof(int32_t);
-    int r = mvo_ensure_pinned(ctx, std::max(bq + bs, (size_t)kMaxIters * 40 + (size_t)n + 64));
+    reset_em_record(state(ctx));
+    if (n >= 5 && cap < n)
+        return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_find_essential_inliers: inlier buffer smaller than n", hipSuccess);
+    int r = essential_ransac(ctx, kp_prev, kp_curr, n, fx, fy, cx, cy, prob, threshold);
     if (r) return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    double* q = reinterpret_cast<double*>(ctx->h_pin);
-    for (int i = 0; i < n; ++i) {
-        q[2 * i] = ((double)kp_prev[2 * i] - pcx) / focal;
-        q[2 * i + 1] = ((double)kp_prev[2 * i + 1] - pcy) / focal;
-        q[2 * (size_t)n + 2 * i] = ((double)kp_curr[2 * i] - pcx) / focal;
-        q[2 * (size_t)n + 2 * i + 1] = ((double)kp_curr[2 * i + 1] - pcy) / focal;
-    }
-    int32_t* subsets = reinterpret_cast<int32_t*>(ctx->h_pin + bq);
-    const int total = n == kModel ? 1 : kMaxIters;
-    if (n == kModel)
-        for (int i = 0; i < kModel; ++i) subsets[i] = i;
-    else
-        draw_subsets(n, kMaxIters, subsets);
-    MVO_HIP(hipMemcpyAsync(s->d_emq, q, bq, hipMemcpyHostToDevice, ctx->stream));
-    MVO_HIP(hipMemcpyAsync(s->d_em_subsets, subsets, (size_t)total * 5 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const double thr = threshold / ((focal + focal) / 2);
-    const float thr2 = (float)(thr * thr);
-    const double* d_q1 = s->d_emq;
-    const double* d_q2 = s->d_emq + 2 * (size_t)n;
-    // The hypotheses are evaluated in growing chunks (a chunk costs ~0.25 ms whatever its size: one wave per hypothesis)
-    const int chunk_end[2] = {256, kMaxIters};
-    auto launch = [&](int begin, int end) {
-        return track_launch_em_hypotheses(ctx, d_q1, d_q2, n, s->d_em_subsets + 5 * (size_t)begin, end - begin, thr2,
-                                          s->d_em_E + 90 * (size_t)begin, s->d_em_nm + begin, s->d_em_counts + 10 * (size_t)begin);
-    };
-    if ((r = ransac_chunks(ctx, n, kModel, total, total, 10, prob, chunk_end, s->d_em_counts, launch, s->em_counts, s->em_info)))
-        return r;
-    const int best_it = s->em_info[0], best_m = s->em_info[1];
-    if (best_it < 0) {
+    mvo_track_state* s = state(ctx);
+    if (s->em_info[0] < 0) {
         if (ctx->prof) mvo_prof_collect(ctx);
         return MVO_OK;
     }
     int cnt = 0;
-    if (n == kModel) {
+    if (n == 5) {
         for (int i = 0; i < n; ++i) inliers[cnt++] = i;
     } else {
-        if ((r = track_launch_em_mask(ctx, d_q1, d_q2, n, s->d_em_E + 90 * (size_t)best_it + 9 * (size_t)best_m, thr2,
-                                      s->d_em_mask)))
-            return r;
         MVO_HIP(hipMemcpyAsync(ctx->h_pin, s->d_em_mask, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
         MVO_HIP(hipStreamSynchronize(ctx->stream));
         for (int i = 0; i < n; ++i)
@@ -700,6 +772,181 @@ int mvo_find_essential_inliers(mvo_ctx* ctx, const float* kp_prev, const float* 
     }
     if (ctx->prof) mvo_prof_collect(ctx);
     *n_inliers = cnt;
+    return MVO_OK;
+}
+
+// estiMotionByEssential (epipolar_geometry.cpp:17-57): findEssentialMat as above, E /= E(2,2), the inlier list
+// from the RANSAC mask, recoverPose(E, pts1, pts2, R, t, focal, pp, mask), t / |t|.  E stays on the device
+// between the RANSAC and k_recover_pose; one read-back brings the result, the counts and the masks.
+int mvo_esti_motion_by_essential(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy,
+                                 double cx, double cy, double prob, double threshold, double* E, double* R, double* t,
+                                 int32_t* inliers, int cap, int* n_inliers, int* found) {
+    if (!ctx || n < 0 || !E || !R || !t || !n_inliers || !found || cap < 0 || (n && (!pts1 || !pts2)) ||
+        (cap && !inliers))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "bad arguments", hipSuccess);
+    if (!(prob > 0 && prob < 1))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_esti_motion_by_essential: prob must be in (0, 1)", hipSuccess);
+    *n_inliers = 0;
+    *found = 0;
+    for (int k = 0; k < 9; ++k) E[k] = R[k] = 0;
+    for (int k = 0; k < 3; ++k) t[k] = 0;
+    mvo_track_state* s = state(ctx);
+    s->rp_n = 0;
+    s->rp_chosen = -1;
+    for (int k = 0; k < 4; ++k) s->rp_good[k] = 0;
+    for (int k = 0; k < 21; ++k) s->rp_R1R2t[k] = 0;
+    reset_em_record(s);
+    if (n >= 5 && cap < n)
+        return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_esti_motion_by_essential: inlier buffer smaller than n", hipSuccess);
+    int r = essential_ransac(ctx, pts1, pts2, n, fx, fy, cx, cy, prob, threshold);
+    if (r) return r;
+    const int best_it = s->em_info[0], best_m = s->em_info[1];
+    // n == 5 with several candidates: findEssentialMat returns them stacked (3k x 3) and decomposeEssentialMat asserts
+    // (deviation 7): no model
+    int n_candidates = 0;
+    if (n == 5 && !s->em_counts.empty())
+        for (int m = 0; m < 10; ++m) n_candidates += s->em_counts[m] >= 0;
+    if (best_it < 0 || n_candidates > 1) {
+        if (ctx->prof) mvo_prof_collect(ctx);
+        return MVO_OK;
+    }
+    if (n > s->cap_rp) {
+        free_dev(s->d_rp_masks);
+        s->cap_rp = 0;
+        const int c = std::max(4096, n + n / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_rp_masks, (size_t)c));
+        s->cap_rp = c;
+    }
+    if (!s->d_rp_out) {
+        MVO_HIP(hipMalloc((void**)&s->d_rp_out, 48 * sizeof(double)));
+        MVO_HIP(hipMalloc((void**)&s->d_rp_cnt, 8 * sizeof(int32_t)));
+    }
+    const double* d_q1 = s->d_emq;
+    const double* d_q2 = s->d_emq + 2 * (size_t)n;
+    if ((r = track_launch_recover_pose(ctx, d_q1, d_q2, n, s->d_em_E + 90 * (size_t)best_it + 9 * (size_t)best_m,
+                                       n == 5 ? nullptr : s->d_em_mask, s->d_rp_masks, s->d_rp_cnt, s->d_rp_out)))
+        return r;
+    // staging: out (42 doubles), counts (6 ints), the recoverPose masks (n), the RANSAC mask (n)
+    double* h_out = reinterpret_cast<double*>(ctx->h_pin);
+    int32_t* h_cnt = reinterpret_cast<int32_t*>(ctx->h_pin + 384);
+    uint8_t* h_masks = ctx->h_pin + 448;
+    uint8_t* h_ransac = h_masks + n;
+    MVO_HIP(hipMemcpyAsync(h_out, s->d_rp_out, 42 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(h_cnt, s->d_rp_cnt, 6 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(h_masks, s->d_rp_masks, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 5) MVO_HIP(hipMemcpyAsync(h_ransac, s->d_em_mask, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) mvo_prof_collect(ctx);
+    int cnt = 0;
+    for (int i = 0; i < n; ++i)
+        if (n == 5 || h_ransac[i]) inliers[cnt++] = i;
+    for (int k = 0; k < 9; ++k) {
+        E[k] = h_out[k];
+        R[k] = h_out[9 + k];
+    }
+    for (int k = 0; k < 3; ++k) t[k] = h_out[18 + k];
+    std::memcpy(s->rp_R1R2t, h_out + 21, sizeof(s->rp_R1R2t));
+    std::memcpy(s->rp_good, h_cnt, sizeof(s->rp_good));
+    s->rp_chosen = h_cnt[5];
+    s->rp_masks.assign(h_masks, h_masks + n);
+    s->rp_n = n;
+    *n_inliers = cnt;
+    *found = 1;
+    return MVO_OK;
+}
+
+int mvo_debug_get_recover_pose(mvo_ctx* ctx, int32_t* good, int32_t* chosen, double* R1R2t, uint8_t* masks, int cap) {
+    if (!ctx || !ctx->track) return mvo_set_err(ctx, MVO_ERR_STATE, "no recoverPose call on this ctx yet", hipSuccess);
+    const mvo_track_state* s = ctx->track;
+    if (good) std::memcpy(good, s->rp_good, sizeof(s->rp_good));
+    if (chosen) *chosen = s->rp_chosen;
+    if (R1R2t) std::memcpy(R1R2t, s->rp_R1R2t, sizeof(s->rp_R1R2t));
+    if (s->rp_n > cap) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_debug_get_recover_pose: buffer too small", hipSuccess);
+    if (masks && s->rp_n) std::memcpy(masks, s->rp_masks.data(), (size_t)s->rp_n);
+    return s->rp_n;
+}
+
+// checkEssentialScore + checkHomographyScore (motion_estimation.cpp:501-664) with their 3 x 3 set-up on the host:
+// K.inv() and H21.inv() by cv::invert's closed form for n <= 3 (invert3), F21 = (Kinv^T E) Kinv.
+int mvo_check_init_scores(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy, double cx,
+                          double cy, const double* E, const int32_t* inl_e, int n_e, const double* H,
+                          const int32_t* inl_h, int n_h, double sigma, double* score_e, double* score_h, int32_t* kept_e,
+                          int* n_kept_e, int32_t* kept_h, int* n_kept_h) {
+    if (!ctx || n < 0 || n_e < 0 || n_h < 0 || !score_e || !score_h || !n_kept_e || !n_kept_h ||
+        (n && (!pts1 || !pts2)) || (E && n_e && (!inl_e || !kept_e)) || (H && n_h && (!inl_h || !kept_h)))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "bad arguments", hipSuccess);
+    const int me = E ? n_e : 0, mh = H ? n_h : 0;
+    for (int i = 0; i < me; ++i)
+        if (inl_e[i] < 0 || inl_e[i] >= n) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_check_init_scores: E list index out of range", hipSuccess);
+    for (int i = 0; i < mh; ++i)
+        if (inl_h[i] < 0 || inl_h[i] >= n) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_check_init_scores: H list index out of range", hipSuccess);
+    *score_e = *score_h = 0;
+    *n_kept_e = *n_kept_h = 0;
+    if (me + mh == 0) return MVO_OK;
+    InitScoreArgs a{};
+    a.inv_s2 = 1.0 / (sigma * sigma);
+    a.has_e = E ? 1 : 0;
+    a.has_h = H ? 1 : 0;
+    if (E) {
+        const double K[9] = {fx, 0, cx, 0, fy, cy, 0, 0, 1};
+        double Ki[9], KiT[9], T[9];
+        invert3(K, Ki);
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) KiT[3 * i + j] = Ki[3 * j + i];
+        mul3(KiT, E, T);
+        mul3(T, Ki, a.f);
+    }
+    if (H) {
+        for (int k = 0; k < 9; ++k) a.h[k] = H[k];
+        invert3(H, a.hi);
+    }
+    MVO_HIP(hipSetDevice(ctx->device));
+    mvo_track_state* s = state(ctx);
+    const size_t bp = (size_t)n * 16, bl = (size_t)(me + mh) * 4;
+    if (bp + bl > s->cap_sc) {
+        free_dev(s->d_sc_in);
+        s->cap_sc = 0;
+        const size_t c = std::max<size_t>(1 << 16, bp + bl + (bp + bl) / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_sc_in, c));
+        s->cap_sc = c;
+    }
+    if ((size_t)(me + mh) > s->cap_sc_kept) {
+        free_dev(s->d_sc_kept);
+        s->cap_sc_kept = 0;
+        const size_t c = std::max<size_t>(4096, (size_t)(me + mh) * 3 / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_sc_kept, c * 4));
+        s->cap_sc_kept = c;
+    }
+    if (!s->d_sc_out) MVO_HIP(hipMalloc((void**)&s->d_sc_out, 64));
+    const size_t o_out = (bp + bl + 63) / 64 * 64;
+    int r = mvo_ensure_pinned(ctx, o_out + 64 + (size_t)(me + mh) * 4);
+    if (r) return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(ctx->h_pin, pts1, (size_t)n * 8);
+    std::memcpy(ctx->h_pin + (size_t)n * 8, pts2, (size_t)n * 8);
+    if (me) std::memcpy(ctx->h_pin + bp, inl_e, (size_t)me * 4);
+    if (mh) std::memcpy(ctx->h_pin + bp + (size_t)me * 4, inl_h, (size_t)mh * 4);
+    MVO_HIP(hipMemcpyAsync(s->d_sc_in, ctx->h_pin, bp + bl, hipMemcpyHostToDevice, ctx->stream));
+    const float* d_p1 = reinterpret_cast<const float*>(s->d_sc_in);
+    const float* d_p2 = reinterpret_cast<const float*>(s->d_sc_in + (size_t)n * 8);
+    const int32_t* d_lists = reinterpret_cast<const int32_t*>(s->d_sc_in + bp);
+    double* d_scores = reinterpret_cast<double*>(s->d_sc_out);
+    int32_t* d_nk = reinterpret_cast<int32_t*>(s->d_sc_out + 16);
+    if ((r = track_launch_init_scores(ctx, d_p1, d_p2, d_lists, me, mh, a, d_scores, s->d_sc_kept, d_nk))) return r;
+    uint8_t* h_out = ctx->h_pin + o_out;
+    int32_t* h_kept = reinterpret_cast<int32_t*>(h_out + 64);
+    MVO_HIP(hipMemcpyAsync(h_out, s->d_sc_out, 24, hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(h_kept, s->d_sc_kept, (size_t)(me + mh) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) mvo_prof_collect(ctx);
+    const double* sc = reinterpret_cast<const double*>(h_out);
+    const int32_t* nk = reinterpret_cast<const int32_t*>(h_out + 16);
+    *score_e = sc[0];
+    *score_h = sc[1];
+    *n_kept_e = nk[0];
+    *n_kept_h = nk[1];
+    if (nk[0]) std::memcpy(kept_e, h_kept, (size_t)nk[0] * 4);
+    if (nk[1]) std::memcpy(kept_h, h_kept + me, (size_t)nk[1] * 4);
     return MVO_OK;
 }
 

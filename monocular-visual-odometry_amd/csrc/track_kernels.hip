@@ -10,6 +10,8 @@
 //   k_h_hypotheses     the RANSAC loop of cv::findHomography (estiMotionByHomography, monocular initialisation): one
 //   k_h_mask           wave per 4-point DLT hypothesis; the inlier mask of the selected one;
 //   k_h_refine         the DLT on all inliers + LMSolver (10 iterations) that findHomography runs after RANSAC.
+//   k_recover_pose     recoverPose after findEssentialMat (estiMotionByEssential): one lane per (match, combination).
+//   k_init_scores      checkEssentialScore and checkHomographyScore (the E/H choice of the initialisation).
 // The arithmetic lives in pnp_wave.h (wave-level SPMD code); this file binds it to threads and LDS.
 #include "mvo_internal.h"
 
@@ -349,6 +351,135 @@ int track_launch_h_refine(mvo_ctx* ctx, const float* d_src, const float* d_dst, 
                           const double* d_H, double* d_out) {
     ProfScope ps(ctx, "k_h_refine");
     hipLaunchKernelGGL(k_h_refine, dim3(1), dim3(pw::kHLanes), 0, ctx->stream, d_src, d_dst, d_mask, n, d_H, d_out);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ recoverPose
+// One lane per (match i, combination c): lane g of the grid takes i = g / 4, c = g % 4.  Every lane scales E and
+// decomposes it itself (uniform, a few hundred flops).  mask[i] gets bit c when the match passes combination c and
+// the RANSAC mask (NULL: every match is a RANSAC inlier).  The four counts are integer sums (exact in any order): per
+// wave a ballot, per workgroup an add, across workgroups an atomic add; the last workgroup to arrive makes the choice.
+// cnt: [0..3] counts, [4] arrivals (both zero on entry), [5] chosen combination.  out: E (scaled, 9), R (9), t (3),
+// R1 R2 t of the decomposition (21).
+__global__ __launch_bounds__(256) void k_recover_pose(const double* __restrict__ q1, const double* __restrict__ q2, int n,
+                                                      const double* __restrict__ E_raw,
+                                                      const uint8_t* __restrict__ ransac_mask, uint8_t* __restrict__ masks,
+                                                      int32_t* cnt, double* __restrict__ out) {
+    __shared__ uint8_t bits[256];
+    __shared__ int wave_cnt[4][4];
+    __shared__ int last;
+    const int t = threadIdx.x;
+    double e_raw[9], E[9], D[21];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) e_raw[k] = E_raw[k];
+    pw::rp_scale9(e_raw, e_raw[8], E);
+    pw::decompose_essential(E, D);
+    const int g = blockIdx.x * 256 + t, i = g >> 2, c = g & 3;
+    bool pass = false;
+    if (i < n) {
+        double P[12];
+        pw::rp_combination(D, c, P);
+        pass = pw::rp_cheirality(q1[2 * i], q1[2 * i + 1], q2[2 * i], q2[2 * i + 1], P, pw::kRpDistanceThresh) &&
+               (!ransac_mask || ransac_mask[i]);
+    }
+    bits[t] = pass ? (uint8_t)(1u << c) : (uint8_t)0;
+    const unsigned long long b = __ballot(pass);
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wave_cnt[t >> 6][k] = __popcll(b & (0x1111111111111111ull << k));
+    }
+    __syncthreads();
+    if (t < 64) {
+        const int m = blockIdx.x * 64 + t;
+        if (m < n) masks[m] = bits[4 * t] | bits[4 * t + 1] | bits[4 * t + 2] | bits[4 * t + 3];
+    }
+    if (t == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            __hip_atomic_fetch_add(cnt + k, wave_cnt[0][k] + wave_cnt[1][k] + wave_cnt[2][k] + wave_cnt[3][k],
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        last = __hip_atomic_fetch_add(cnt + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last || t != 0) return;
+    __threadfence();
+    int32_t good[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) good[k] = __hip_atomic_load(cnt + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int chosen = pw::rp_choose(good);
+    double R[9], tn[3];
+    pw::rp_finish(D, chosen, R, tn);
+    for (int k = 0; k < 9; ++k) out[k] = E[k];
+    for (int k = 0; k < 9; ++k) out[9 + k] = R[k];
+    for (int k = 0; k < 3; ++k) out[18 + k] = tn[k];
+    for (int k = 0; k < 21; ++k) out[21 + k] = D[k];
+    cnt[5] = chosen;
+}
+
+int track_launch_recover_pose(mvo_ctx* ctx, const double* d_q1, const double* d_q2, int n, const double* d_E,
+                              const uint8_t* d_ransac_mask, uint8_t* d_masks, int32_t* d_cnt, double* d_out) {
+    MVO_HIP(hipMemsetAsync(d_cnt, 0, 6 * sizeof(int32_t), ctx->stream));
+    ProfScope ps(ctx, "k_recover_pose");
+    hipLaunchKernelGGL(k_recover_pose, dim3((n + 63) / 64), dim3(256), 0, ctx->stream, d_q1, d_q2, n, d_E, d_ransac_mask,
+                       d_masks, d_cnt, d_out);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ E / H scores
+// Workgroup 0 scores the E list, workgroup 1 the H list, one wave each.  Lane l takes the list positions
+// l, l + 64, ... (one lane per listed match) and accumulates its terms from 0.0, term 1 before term 2; the 64
+// partials are then added in lane order.  The kept entries are appended in list order (ballot prefix per round).
+__global__ __launch_bounds__(64) void k_init_scores(const float2* __restrict__ kp1, const float2* __restrict__ kp2,
+                                                    const int32_t* __restrict__ lists, int n_e, int n_h, InitScoreArgs a,
+                                                    double* __restrict__ scores, int32_t* __restrict__ kept,
+                                                    int32_t* __restrict__ n_kept) {
+    __shared__ double part[64];
+    const int which = blockIdx.x, l = threadIdx.x;
+    const int32_t* list = lists + (which ? n_e : 0);
+    int32_t* out = kept + (which ? n_e : 0);
+    const int m = which ? (a.has_h ? n_h : 0) : (a.has_e ? n_e : 0);
+    double acc = 0.0;
+    int base = 0;
+    for (int start = 0; start < m; start += 64) {
+        const int i = start + l;
+        bool good = false;
+        if (i < m) {
+            const int j = list[i];
+            const double u1 = kp1[j].x, v1 = kp1[j].y, u2 = kp2[j].x, v2 = kp2[j].y;
+            double t1, t2;
+            if (which == 0) {
+                pw::score_e_terms(a.f, u1, v1, u2, v2, a.inv_s2, &t1, &t2, &good);
+                acc = acc + t1;
+                acc = acc + t2;
+            } else {
+                bool add1, add2;
+                pw::score_h_terms(a.h, a.hi, u1, v1, u2, v2, a.inv_s2, &t1, &add1, &t2, &add2, &good);
+                if (add1) acc = acc + t1;
+                if (add2) acc = acc + t2;
+            }
+        }
+        const unsigned long long b = __ballot(good);
+        if (good) out[base + __popcll(b & ((1ull << l) - 1ull))] = list[i];
+        base += __popcll(b);
+    }
+    part[l] = acc;
+    __syncthreads();
+    if (l == 0) {
+        double s = 0.0;
+        for (int q = 0; q < 64; ++q) s = s + part[q];
+        scores[which] = s;
+        n_kept[which] = base;
+    }
+}
+
+int track_launch_init_scores(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, const int32_t* d_lists, int n_e,
+                             int n_h, const InitScoreArgs& a, double* d_scores, int32_t* d_kept, int32_t* d_n_kept) {
+    ProfScope ps(ctx, "k_init_scores");
+    hipLaunchKernelGGL(k_init_scores, dim3(2), dim3(64), 0, ctx->stream, (const float2*)d_kp1, (const float2*)d_kp2,
+                       d_lists, n_e, n_h, a, d_scores, d_kept, d_n_kept);
     MVO_HIP(hipGetLastError());
     return MVO_OK;
 }

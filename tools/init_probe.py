@@ -1,7 +1,10 @@
 """Wall time of mvo_find_homography (host clock around the synchronous call, warmed up, >= 50 repeats) at 500 / 1000 / 2000
 matches with 0 / 50 % wrong matches, beside the sequential CPU restatement of the same call (tests/homography_restatement.cpp).
+--essential: the same for mvo_esti_motion_by_essential (thick scene) beside mvo_find_essential_inliers on the same matches
+(the difference is what recoverPose adds), and mvo_check_init_scores on both models, beside the restatement
+(tests/init_motion_restatement.cpp; its RANSAC stage is the CPU oracle's).
 Per-kernel device times: run it under rocprofv3 --kernel-trace --stats.
-Usage: python tools/init_probe.py [--reps 50] [--out FILE]"""
+Usage: python tools/init_probe.py [--essential] [--reps 50] [--out FILE]"""
 import argparse
 import json
 import os
@@ -15,6 +18,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as graft  # noqa: E402
 import h_restate as HR  # noqa: E402
+import init_restate as IR  # noqa: E402
 
 
 def timed(fn, reps):
@@ -32,12 +36,35 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--essential", action="store_true")
     a = ap.parse_args()
     mvo = graft.load_package()
     ctx = mvo.Context(0)
     R = HR.Restatement()
     rows = []
-    for n in (500, 1000, 2000):
+    if a.essential:
+        O = graft.load_oracle()
+        O.build()
+        IRR = IR.Restatement()
+        for n in (500, 1000, 2000):
+            for frac in (0.0, 0.5):
+                pr = HR.two_view(n, 200 + n, planar=False, noise=0.5, outlier_frac=frac)
+                s, d, K = pr["src"], pr["dst"], IR.kdict(pr["K"])
+                g = ctx.esti_motion_by_essential(s, d, K)
+                h = ctx.find_homography(s, d)
+                H = IR.scale_by_22(h["H"])
+                em_med, _ = timed(lambda: ctx.find_essential_inliers(s, d, K), a.reps)
+                rp_med, rp_min = timed(lambda: ctx.esti_motion_by_essential(s, d, K), a.reps)
+                sc_med, sc_min = timed(lambda: ctx.check_init_scores(s, d, K, g["E"], g["inliers"], H, h["inliers"]), a.reps)
+                cpu_rp, _ = timed(lambda: IRR.esti_motion_by_essential(O, s, d, pr["K"]), max(5, a.reps // 10))
+                cpu_sc, _ = timed(lambda: IRR.check_init_scores(s, d, pr["K"], g["E"], g["inliers"], H, h["inliers"]),
+                                  max(5, a.reps // 10))
+                rows.append(dict(n=n, outliers=frac, n_inl_e=len(g["inliers"]), n_inl_h=len(h["inliers"]),
+                                 find_essential_ms_median=em_med, esti_motion_ms_median=rp_med, esti_motion_ms_min=rp_min,
+                                 scores_ms_median=sc_med, scores_ms_min=sc_min, cpu_esti_motion_ms_median=cpu_rp,
+                                 cpu_scores_ms_median=cpu_sc))
+                print(json.dumps(rows[-1]), flush=True)
+    for n in (() if a.essential else (500, 1000, 2000)):
         for frac in (0.0, 0.5):
             pr = HR.two_view(n, 100 + n, planar=True, noise=0.5, outlier_frac=frac)
             s, d = pr["src"], pr["dst"]
