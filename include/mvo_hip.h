@@ -332,6 +332,53 @@ int mvo_check_init_scores(mvo_ctx* ctx, const float* pts1, const float* pts2, in
                           double cy, const double* E, const int32_t* inl_e, int n_e, const double* H,
                           const int32_t* inl_h, int n_h, double sigma, double* score_e, double* score_h, int32_t* kept_e,
                           int* n_kept_e, int32_t* kept_h, int* n_kept_h);
+/* estiMotionByHomography + removeWrongRtOfHomography (src/geometry/epipolar_geometry.cpp:59-128), the homography
+ * branch of the monocular initialisation: findHomography exactly as mvo_find_homography runs it (H, inliers, cap,
+ * n_inliers and found are that call's outputs, except that H is returned times 1 / H(2,2)), then
+ * decomposeHomographyMat(H, K) (OpenCV's HomographyDecompInria, K = [fx 0 cx; 0 fy cy; 0 0 1]), each t times
+ * 1 / sqrt(t1^2 + t2^2 + t0^2), and filterHomographyDecompByVisibleRefpoints on the inliers' pixel2CamNormPlane
+ * points.  Rs (4 x 9, row-major), ts (4 x 3), normals (4 x 3): the n_solutions surviving candidates in OpenCV's
+ * order (Ra ta na), (Ra -ta -na), (Rb tb nb), (Rb -tb -nb); unused rows are zero.  A rotation-only H decomposes to
+ * one candidate with a zero normal, which the filter removes.  Declared arithmetic: DESIGN.md section 12. */
+int mvo_esti_motion_by_homography(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy,
+                                  double cx, double cy, double threshold, double confidence, double* H,
+                                  int32_t* inliers, int cap, int* n_inliers, double* Rs, double* ts, double* normals,
+                                  int* n_solutions, int* found);
+
+/* Result of mvo_estimate_possible_relative_poses.  The caller sets the four buffers and their capacities; the call
+ * fills the rest.  Slot 0 is the E motion (present[0] = found_e), slots 1 .. n_slots - 1 the surviving H candidates
+ * (h_candidate[s]: their index 0..3 in the decomposition).  The points of slot s are pts3d[pts_offset[s] ..
+ * pts_offset[s] + pts_count[s]) (x, y, z per point, in camera 1), one per entry of the slot's inlier list, slot after
+ * slot.  best: the chosen slot, -1 when the reference's rule picks a slot that does not exist (DESIGN.md section 2,
+ * deviation 11). */
+typedef struct {
+    int32_t* inliers_e; /* capacity cap_inliers >= n */
+    int32_t* inliers_h; /* capacity cap_inliers >= n */
+    int cap_inliers;
+    float* pts3d;       /* capacity cap_pts points: n_inliers_e + 4 n_inliers_h suffices */
+    int cap_pts;
+    double E[9], H[9];  /* E times 1 / E(2,2), H times 1 / H(2,2); zero when absent */
+    int found_e, found_h, n_inliers_e, n_inliers_h;
+    int n_slots;
+    int32_t present[5], h_candidate[5], pts_offset[5], pts_count[5];
+    double R[5][9], t[5][3], normal[5][3]; /* normal of slot 0: zero */
+    double score_e, score_h, ratio;
+    int best;
+} mvo_init_poses;
+
+/* geometry::helperEstimatePossibleRelativePosesByEpipolarGeometry (src/geometry/motion_estimation.cpp:10-157) with
+ * is_calc_homo = true, the entry point of the monocular initialisation: mvo_esti_motion_by_essential (prob,
+ * threshold) and mvo_esti_motion_by_homography (h_threshold, h_confidence) on the same matches, the solution table,
+ * doTriangulation of every slot on its inlier list (the arithmetic of mvo_triangulate_points), the two scores of
+ * mvo_check_init_scores (sigma), ratio = score_h / (score_e + score_h), and the choice: the H slot with the strictly
+ * largest |n_z| when ratio > 0.5 (first slot on ties), else slot 0.  motion_cam2_to_cam1 == 0: every slot's (R, t)
+ * is replaced by the inverse of [R t; 0 1] (basics::invRt, the LU of mvo_invert_pose) after the triangulation.
+ * An absent model scores 0 (deviations 9 and 10).  The E / H records of the single calls
+ * (mvo_debug_get_*) describe this call afterwards. */
+int mvo_estimate_possible_relative_poses(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx,
+                                         double fy, double cx, double cy, double prob, double threshold,
+                                         double h_threshold, double h_confidence, double sigma,
+                                         int motion_cam2_to_cam1, mvo_init_poses* out);
 /* VisualOdometry::retainGoodTriangulationResult_ (src/vo/vo.cpp:181-244), host-side (acos + a sort for the
  * median): keep[i] lists the points whose triangulation angle (degrees) is >= min_triang_angle and at most
  * max_ratio_to_median times the median; angles (n, may be NULL) receives every angle. */
@@ -425,6 +472,13 @@ int mvo_debug_get_homography(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32
  * R1R2t = R1 (9), R2 (9), t (3) of decomposeEssentialMat; masks[i] bit k set when match i passes combination k
  * and the RANSAC mask.  Returns n (the number of masks). */
 int mvo_debug_get_recover_pose(mvo_ctx* ctx, int32_t* good, int32_t* chosen, double* R1R2t, uint8_t* masks, int cap);
+/* Record of the last homography decomposition (mvo_esti_motion_by_homography or mvo_estimate_possible_relative_poses
+ * on this ctx): Hn (9) after its 1 / w[1] scaling, w (3, descending), branch[2] = {1 for the rotation-only branch
+ * else 0, the index of the largest |S_ii| or -1}, the raw candidates Rs (4 x 9), ts (4 x 3, before t / |t|), normals
+ * (4 x 3) and rejected[4], the number of H inliers that reject each candidate (a candidate survives at 0).  Returns
+ * the number of candidates: 0 when there was no H, 1 for the rotation-only branch, else 4. */
+int mvo_debug_get_homography_decomposition(mvo_ctx* ctx, double* Hn, double* w, int32_t* branch, double* Rs,
+                                           double* ts, double* normals, int32_t* rejected);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,16 @@ class MvoError(RuntimeError):
         self.code = code
 
 
+class InitPoses(C.Structure):
+    """mvo_init_poses (include/mvo_hip.h)."""
+    _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
+                ("cap_pts", C.c_int), ("E", C.c_double * 9), ("H", C.c_double * 9), ("found_e", C.c_int),
+                ("found_h", C.c_int), ("n_inliers_e", C.c_int), ("n_inliers_h", C.c_int), ("n_slots", C.c_int),
+                ("present", C.c_int32 * 5), ("h_candidate", C.c_int32 * 5), ("pts_offset", C.c_int32 * 5),
+                ("pts_count", C.c_int32 * 5), ("R", C.c_double * 45), ("t", C.c_double * 15), ("normal", C.c_double * 15),
+                ("score_e", C.c_double), ("score_h", C.c_double), ("ratio", C.c_double), ("best", C.c_int)]
+
+
 _lib = None
 
 
@@ -499,6 +509,72 @@ class Context:
             C.c_double(K["cy"]), _p(Ed), _p(le), len(le), _p(Hd), _p(lh), len(lh), C.c_double(sigma), C.byref(se),
             C.byref(sh), _p(ke), C.byref(ne), _p(kh), C.byref(nh)))
         return dict(score_e=se.value, score_h=sh.value, kept_e=ke[:ne.value].copy(), kept_h=kh[:nh.value].copy())
+
+    def esti_motion_by_homography(self, kp1, kp2, K, threshold=3.0, confidence=0.995):
+        """estiMotionByHomography + removeWrongRtOfHomography -> dict(found, H (scaled by 1 / H(2,2)), inliers
+        (ascending indices of the RANSAC mask), Rs, ts (unit), normals: lists of the surviving candidates)."""
+        a = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
+        assert len(a) == len(b)
+        n = len(a)
+        H, Rs, ts, ns = np.zeros(9), np.zeros(36), np.zeros(12), np.zeros(12)
+        inl = np.zeros(max(n, 1), np.int32)
+        cnt, k, found = C.c_int(), C.c_int(), C.c_int()
+        self._chk(self.lib.mvo_esti_motion_by_homography(
+            self.h, _p(a), _p(b), n, C.c_double(K["fx"]), C.c_double(K["fy"]), C.c_double(K["cx"]), C.c_double(K["cy"]),
+            C.c_double(threshold), C.c_double(confidence), _p(H), _p(inl), len(inl), C.byref(cnt), _p(Rs), _p(ts),
+            _p(ns), C.byref(k), C.byref(found)))
+        ok = bool(found.value)
+        m = k.value
+        return dict(found=ok, H=H.reshape(3, 3) if ok else None, inliers=inl[:cnt.value].copy(),
+                    Rs=[Rs[9 * j:9 * j + 9].reshape(3, 3).copy() for j in range(m)], ts=[ts[3 * j:3 * j + 3].copy() for j in range(m)],
+                    normals=[ns[3 * j:3 * j + 3].copy() for j in range(m)])
+
+    def debug_homography_decomposition(self):
+        """Record of the last homography decomposition: dict(count (0: no H, 1: rotation-only, 4), rotation_only,
+        index (of the largest |S_ii|, -1 for rotation-only), Hn, w, Rs (4 x 3 x 3), ts (4 x 3, before t / |t|), normals
+        (4 x 3), rejected (H inliers rejecting each candidate))."""
+        Hn, w, Rs, ts, ns = np.zeros(9), np.zeros(3), np.zeros(36), np.zeros(12), np.zeros(12)
+        br, rej = np.zeros(2, np.int32), np.zeros(4, np.int32)
+        cnt = self.lib.mvo_debug_get_homography_decomposition(self.h, _p(Hn), _p(w), _p(br), _p(Rs), _p(ts), _p(ns), _p(rej))
+        if cnt < 0:
+            self._chk(cnt)
+        return dict(count=cnt, rotation_only=bool(br[0]), index=int(br[1]), Hn=Hn.reshape(3, 3), w=w,
+                    Rs=Rs.reshape(4, 3, 3), ts=ts.reshape(4, 3), normals=ns.reshape(4, 3), rejected=rej)
+
+    def estimate_possible_relative_poses(self, kp1, kp2, K, prob=0.999, threshold=1.0, h_threshold=3.0,
+                                         h_confidence=0.995, sigma=1.0, motion_cam2_to_cam1=True):
+        """helperEstimatePossibleRelativePosesByEpipolarGeometry (is_calc_homo = true) -> dict(best (-1: the rule picked
+        a slot that does not exist), ratio, score_e, score_h, E, H (None when absent), inliers_e, inliers_h,
+        solutions=[dict(kind "E" / "H", R, t, normal (None for E), inliers, pts3d (in camera 1), candidate (H: index in
+        the decomposition))]).  solutions[0] is the E slot, None when E has no model; best indexes solutions."""
+        a = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
+        assert len(a) == len(b)
+        n = len(a)
+        ie, ih = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        pts = np.zeros((max(5 * n, 1), 3), np.float32)
+        o = InitPoses()
+        o.inliers_e, o.inliers_h, o.cap_inliers = _p(ie), _p(ih), len(ie)
+        o.pts3d, o.cap_pts = _p(pts), len(pts)
+        self._chk(self.lib.mvo_estimate_possible_relative_poses(
+            self.h, _p(a), _p(b), n, C.c_double(K["fx"]), C.c_double(K["fy"]), C.c_double(K["cx"]), C.c_double(K["cy"]),
+            C.c_double(prob), C.c_double(threshold), C.c_double(h_threshold), C.c_double(h_confidence),
+            C.c_double(sigma), int(bool(motion_cam2_to_cam1)), C.byref(o)))
+        ine, inh = ie[:o.n_inliers_e].copy(), ih[:o.n_inliers_h].copy()
+        sols = []
+        for s in range(o.n_slots):
+            if not o.present[s]:
+                sols.append(None)
+                continue
+            off, m = o.pts_offset[s], o.pts_count[s]
+            sols.append(dict(kind="E" if s == 0 else "H", R=np.array(o.R[9 * s:9 * s + 9]).reshape(3, 3),
+                             t=np.array(o.t[3 * s:3 * s + 3]),
+                             normal=None if s == 0 else np.array(o.normal[3 * s:3 * s + 3]), inliers=ine if s == 0 else inh,
+                             pts3d=pts[off:off + m].copy(), candidate=-1 if s == 0 else int(o.h_candidate[s])))
+        return dict(best=int(o.best), ratio=o.ratio, score_e=o.score_e, score_h=o.score_h,
+                    E=np.array(o.E).reshape(3, 3) if o.found_e else None, H=np.array(o.H).reshape(3, 3) if o.found_h else None,
+                    inliers_e=ine, inliers_h=inh, solutions=sols)
 
     def debug_homography(self):
         counts = np.zeros(2000, np.int32)

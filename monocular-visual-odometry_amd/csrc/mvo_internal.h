@@ -140,6 +140,19 @@ struct InitScoreArgs {  // k_init_scores: F21, H21, H12 (row-major), 1 / sigma^2
     double inv_s2;
     int has_e, has_h;
 };
+// k_h_decompose's double output (hd_wave.h, track_host.cpp)
+constexpr int kHdHs = 0;   // H * (1 / H(2,2)), 9
+constexpr int kHdHn = 9;   // Hn after the 1 / w[1] scaling, 9
+constexpr int kHdW = 18;   // singular values of (K^-1 H) K, 3
+constexpr int kHdR = 21;   // R of the 4 raw candidates, 4 x 9
+constexpr int kHdT = 57;   // t of the 4 raw candidates (before normalisation), 4 x 3
+constexpr int kHdN = 69;   // n of the 4 raw candidates, 4 x 3
+constexpr int kHdTn = 81;  // t / |t| of the 4 candidates, 4 x 3
+constexpr int kHdOut = 93;
+// its int output: [0..3] rejecting matches per candidate, [4] arrivals (both zeroed by the launch), [5] number of
+// candidates (1: rotation-only, 4: general), [6] branch (-1: rotation-only, else the index of the largest |S_ii|),
+// [7] number of survivors, [8..11] their indices in candidate order
+constexpr int kHdCnt = 12;
 struct TrackViewArgs {
     double T[12];  // rows 0..2 of T_c_w = inv(T_w_c)
     double fx, fy, cx, cy;
@@ -292,6 +305,11 @@ int track_launch_recover_pose(mvo_ctx* ctx, const double* d_q1, const double* d_
                               const uint8_t* d_ransac_mask, uint8_t* d_masks, int32_t* d_cnt, double* d_out);
 int track_launch_init_scores(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, const int32_t* d_lists, int n_e,
                              int n_h, const InitScoreArgs& a, double* d_scores, int32_t* d_kept, int32_t* d_n_kept);
+int track_launch_h_decompose(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, const uint8_t* d_mask, int n,
+                             const double* d_H, const TrackCamera& cam, int32_t* d_cnt, double* d_out);
+int track_launch_init_triangulate(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, int n, const TrackCamera& cam,
+                                  const double* d_e_out, const uint8_t* d_e_mask, const double* d_h_out,
+                                  const int32_t* d_h_cnt, const uint8_t* d_h_mask, float* d_pts);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -66,6 +66,14 @@ struct mvo_track_state {
     int32_t* d_sc_kept = nullptr;
     size_t cap_sc_kept = 0;
     uint8_t* d_sc_out = nullptr;  // 2 scores, 2 kept counts
+    // homography decomposition (record of the last call: mvo_debug_get_homography_decomposition) and the
+    // triangulation of the initialisation's solutions ([5][n] points)
+    double* d_hd_out = nullptr;
+    int32_t* d_hd_cnt = nullptr;
+    double hd_out[kHdOut] = {};
+    int32_t hd_cnt[kHdCnt] = {};
+    float* d_ip_pts = nullptr;
+    size_t cap_ip_pts = 0;
     // map points in view
     uint8_t* d_view_desc = nullptr;
     int32_t* d_view_n = nullptr;
@@ -410,6 +418,49 @@ void mul3(const double* A, const double* B, double* C) {
         }
 }
 
+int ensure_tri(mvo_ctx* ctx, int n) {
+    mvo_track_state* s = state(ctx);
+    if (n > s->cap_tri) {
+        free_dev(s->d_tri_in);
+        free_dev(s->d_tri_out);
+        s->cap_tri = 0;
+        const int cap = std::max(4096, n + n / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_tri_in, (size_t)cap * 4 * sizeof(float)));
+        MVO_HIP(hipMalloc((void**)&s->d_tri_out, (size_t)cap * 6 * sizeof(float)));
+        s->cap_tri = cap;
+    }
+    return MVO_OK;
+}
+
+int ensure_hd(mvo_ctx* ctx) {
+    mvo_track_state* s = state(ctx);
+    if (!s->d_hd_out) {
+        MVO_HIP(hipMalloc((void**)&s->d_hd_out, kHdOut * sizeof(double)));
+        MVO_HIP(hipMalloc((void**)&s->d_hd_cnt, kHdCnt * sizeof(int32_t)));
+    }
+    return MVO_OK;
+}
+
+void reset_hd_record(mvo_track_state* s) {
+    for (double& v : s->hd_out) v = 0;
+    for (int32_t& v : s->hd_cnt) v = 0;
+}
+
+// The H that mvo_find_homography left on the device (found == 1) and its RANSAC mask (NULL: all four matches)
+const double* device_h(const mvo_track_state* s, int n) { return n == 4 ? s->d_h_H + 9 * (size_t)s->h_info[0] : s->d_h_out; }
+const uint8_t* device_h_mask(const mvo_track_state* s, int n) { return n == 4 ? nullptr : s->d_h_mask; }
+
+// basics::invRt: [R t; 0 1].inv() by the LU of mvo_invert_pose (cv::Mat::inv leaves zeros for a singular matrix)
+void inv_rt(double* R, double* t) {
+    double T[16] = {R[0], R[1], R[2], t[0], R[3], R[4], R[5], t[1], R[6], R[7], R[8], t[2], 0, 0, 0, 1}, Ti[16];
+    if (!invert_pose_lu(T, Ti, 4))
+        for (double& v : Ti) v = 0;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) R[3 * i + j] = Ti[4 * i + j];
+        t[i] = Ti[4 * i + 3];
+    }
+}
+
 }  // namespace
 
 void track_release(mvo_ctx* ctx) {
@@ -443,6 +494,9 @@ void track_release(mvo_ctx* ctx) {
     free_dev(s->d_sc_in);
     free_dev(s->d_sc_kept);
     free_dev(s->d_sc_out);
+    free_dev(s->d_hd_out);
+    free_dev(s->d_hd_cnt);
+    free_dev(s->d_ip_pts);
     delete s;
     ctx->track = nullptr;
 }
@@ -715,16 +769,9 @@ int mvo_triangulate_points(mvo_ctx* ctx, const float* kp_prev, const float* kp_c
     if (n == 0) return MVO_OK;
     MVO_HIP(hipSetDevice(ctx->device));
     mvo_track_state* s = state(ctx);
-    if (n > s->cap_tri) {
-        free_dev(s->d_tri_in);
-        free_dev(s->d_tri_out);
-        s->cap_tri = 0;
-        const int cap = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_tri_in, (size_t)cap * 4 * sizeof(float)));
-        MVO_HIP(hipMalloc((void**)&s->d_tri_out, (size_t)cap * 6 * sizeof(float)));
-        s->cap_tri = cap;
-    }
-    int r = mvo_ensure_pinned(ctx, (size_t)n * 24);
+    int r = ensure_tri(ctx, n);
+    if (r) return r;
+    r = mvo_ensure_pinned(ctx, (size_t)n * 24);
     if (r) return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));
     std::memcpy(ctx->h_pin, kp_prev, (size_t)n * 8);
@@ -1067,6 +1114,210 @@ int mvo_debug_get_homography(mvo_ctx* ctx, int32_t* counts, int cap_iters, int32
     if (iters > cap_iters) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_debug_get_homography: buffer too small", hipSuccess);
     if (counts && iters) std::memcpy(counts, s->h_counts.data(), (size_t)iters * 4);
     return iters;
+}
+
+// estiMotionByHomography + removeWrongRtOfHomography (epipolar_geometry.cpp:59-128): mvo_find_homography, then
+// k_h_decompose on the H and mask it left on the device; one read-back brings H / H(2,2), the decomposition, the
+// rejection counts and the survivors.
+int mvo_esti_motion_by_homography(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy,
+                                  double cx, double cy, double threshold, double confidence, double* H,
+                                  int32_t* inliers, int cap, int* n_inliers, double* Rs, double* ts, double* normals,
+                                  int* n_solutions, int* found) {
+    if (!ctx || !Rs || !ts || !normals || !n_solutions) return mvo_set_err(ctx, MVO_ERR_INVALID, "bad arguments", hipSuccess);
+    *n_solutions = 0;
+    for (int k = 0; k < 36; ++k) Rs[k] = 0;
+    for (int k = 0; k < 12; ++k) ts[k] = normals[k] = 0;
+    reset_hd_record(state(ctx));
+    int r = mvo_find_homography(ctx, pts1, pts2, n, threshold, confidence, H, inliers, cap, n_inliers, found);
+    if (r || !*found) return r;
+    mvo_track_state* s = state(ctx);
+    if ((r = ensure_hd(ctx))) return r;
+    const TrackCamera cam{fx, fy, cx, cy};
+    if ((r = track_launch_h_decompose(ctx, s->d_hpts, s->d_hpts + 2 * (size_t)n, device_h_mask(s, n), n, device_h(s, n), cam,
+                                      s->d_hd_cnt, s->d_hd_out)))
+        return r;
+    double* h_out = reinterpret_cast<double*>(ctx->h_pin);
+    int32_t* h_cnt = reinterpret_cast<int32_t*>(ctx->h_pin + kHdOut * sizeof(double));
+    MVO_HIP(hipMemcpyAsync(h_out, s->d_hd_out, kHdOut * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(h_cnt, s->d_hd_cnt, kHdCnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) mvo_prof_collect(ctx);
+    std::memcpy(s->hd_out, h_out, sizeof(s->hd_out));
+    std::memcpy(s->hd_cnt, h_cnt, sizeof(s->hd_cnt));
+    for (int k = 0; k < 9; ++k) H[k] = s->hd_out[kHdHs + k];
+    const int k_surv = s->hd_cnt[7];
+    for (int j = 0; j < k_surv; ++j) {
+        const int c = s->hd_cnt[8 + j];
+        for (int k = 0; k < 9; ++k) Rs[9 * j + k] = s->hd_out[kHdR + 9 * c + k];
+        for (int k = 0; k < 3; ++k) {
+            ts[3 * j + k] = s->hd_out[kHdTn + 3 * c + k];
+            normals[3 * j + k] = s->hd_out[kHdN + 3 * c + k];
+        }
+    }
+    *n_solutions = k_surv;
+    return MVO_OK;
+}
+
+int mvo_debug_get_homography_decomposition(mvo_ctx* ctx, double* Hn, double* w, int32_t* branch, double* Rs,
+                                           double* ts, double* normals, int32_t* rejected) {
+    if (!ctx || !ctx->track) return mvo_set_err(ctx, MVO_ERR_STATE, "no homography decomposition on this ctx yet", hipSuccess);
+    const mvo_track_state* s = ctx->track;
+    const int count = s->hd_cnt[5];
+    if (Hn) std::memcpy(Hn, s->hd_out + kHdHn, 9 * sizeof(double));
+    if (w) std::memcpy(w, s->hd_out + kHdW, 3 * sizeof(double));
+    if (branch) {
+        branch[0] = count == 1 ? 1 : 0;
+        branch[1] = count == 4 ? s->hd_cnt[6] : -1;
+    }
+    if (Rs) std::memcpy(Rs, s->hd_out + kHdR, 36 * sizeof(double));
+    if (ts) std::memcpy(ts, s->hd_out + kHdT, 12 * sizeof(double));
+    if (normals) std::memcpy(normals, s->hd_out + kHdN, 12 * sizeof(double));
+    if (rejected) std::memcpy(rejected, s->hd_cnt, 4 * sizeof(int32_t));
+    return count;
+}
+
+// helperEstimatePossibleRelativePosesByEpipolarGeometry (motion_estimation.cpp:10-157), is_calc_homo = true.  The E
+// and H branches run as the single calls do and leave their models and masks on the device; k_h_decompose and
+// k_init_triangulate (every slot in one launch) follow in stream order, and one read-back brings the decomposition and
+// the points.  The scores are mvo_check_init_scores on the two lists; the choice and invRt are host scalars.
+int mvo_estimate_possible_relative_poses(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx,
+                                         double fy, double cx, double cy, double prob, double threshold,
+                                         double h_threshold, double h_confidence, double sigma,
+                                         int motion_cam2_to_cam1, mvo_init_poses* out) {
+    if (!ctx || !out || n < 0 || (n && (!pts1 || !pts2)) || out->cap_inliers < 0 || out->cap_pts < 0 ||
+        (out->cap_inliers && (!out->inliers_e || !out->inliers_h)) || (out->cap_pts && !out->pts3d))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "bad arguments", hipSuccess);
+    if (out->cap_inliers < n)
+        return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_estimate_possible_relative_poses: inlier buffers smaller than n", hipSuccess);
+    for (int k = 0; k < 9; ++k) out->E[k] = out->H[k] = 0;
+    out->found_e = out->found_h = out->n_inliers_e = out->n_inliers_h = 0;
+    out->n_slots = 1;
+    for (int j = 0; j < 5; ++j) {
+        out->present[j] = 0;
+        out->h_candidate[j] = -1;
+        out->pts_offset[j] = out->pts_count[j] = 0;
+        for (int k = 0; k < 9; ++k) out->R[j][k] = 0;
+        for (int k = 0; k < 3; ++k) out->t[j][k] = out->normal[j][k] = 0;
+    }
+    out->score_e = out->score_h = out->ratio = 0;
+    out->best = -1;
+    mvo_track_state* s = state(ctx);
+    reset_hd_record(s);
+    // estiMotionByEssential, then estiMotionByHomography (the reference's order)
+    double R_e[9], t_e[3], H_raw[9];
+    int r = mvo_esti_motion_by_essential(ctx, pts1, pts2, n, fx, fy, cx, cy, prob, threshold, out->E, R_e, t_e,
+                                         out->inliers_e, out->cap_inliers, &out->n_inliers_e, &out->found_e);
+    if (r) return r;
+    r = mvo_find_homography(ctx, pts1, pts2, n, h_threshold, h_confidence, H_raw, out->inliers_h, out->cap_inliers,
+                            &out->n_inliers_h, &out->found_h);
+    if (r) return r;
+    if (n == 0) {  // no model, no slot: both scores 0, a NaN ratio, best = -1
+        out->ratio = out->score_h / (out->score_e + out->score_h);
+        return MVO_OK;
+    }
+    if ((r = ensure_tri(ctx, n)) || (r = ensure_hd(ctx))) return r;
+    const size_t n_pts = (size_t)5 * n * 3;
+    if (n_pts > s->cap_ip_pts) {
+        free_dev(s->d_ip_pts);
+        s->cap_ip_pts = 0;
+        const size_t c = std::max<size_t>(1 << 16, n_pts + n_pts / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_ip_pts, c * sizeof(float)));
+        s->cap_ip_pts = c;
+    }
+    const size_t o_out = ((size_t)n * 16 + 63) / 64 * 64, o_pts = o_out + 1024;  // out (744 B), cnt (48 B), points
+    if ((r = mvo_ensure_pinned(ctx, o_pts + n_pts * sizeof(float)))) return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    std::memcpy(ctx->h_pin, pts1, (size_t)n * 8);
+    std::memcpy(ctx->h_pin + (size_t)n * 8, pts2, (size_t)n * 8);
+    MVO_HIP(hipMemcpyAsync(s->d_tri_in, ctx->h_pin, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    const float* d_p1 = s->d_tri_in;
+    const float* d_p2 = s->d_tri_in + 2 * (size_t)n;
+    const TrackCamera cam{fx, fy, cx, cy};
+    if (out->found_h &&
+        (r = track_launch_h_decompose(ctx, d_p1, d_p2, device_h_mask(s, n), n, device_h(s, n), cam, s->d_hd_cnt, s->d_hd_out)))
+        return r;
+    if ((r = track_launch_init_triangulate(ctx, d_p1, d_p2, n, cam, out->found_e ? s->d_rp_out : nullptr,
+                                           n == 5 ? nullptr : s->d_em_mask, out->found_h ? s->d_hd_out : nullptr,
+                                           s->d_hd_cnt, device_h_mask(s, n), s->d_ip_pts)))
+        return r;
+    double* h_out = reinterpret_cast<double*>(ctx->h_pin + o_out);
+    int32_t* h_cnt = reinterpret_cast<int32_t*>(ctx->h_pin + o_out + kHdOut * sizeof(double));
+    float* h_pts = reinterpret_cast<float*>(ctx->h_pin + o_pts);
+    if (out->found_h) {
+        MVO_HIP(hipMemcpyAsync(h_out, s->d_hd_out, kHdOut * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        MVO_HIP(hipMemcpyAsync(h_cnt, s->d_hd_cnt, kHdCnt * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (out->found_e || out->found_h)
+        MVO_HIP(hipMemcpyAsync(h_pts, s->d_ip_pts, n_pts * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    if (ctx->prof) mvo_prof_collect(ctx);
+    if (out->found_h) {
+        std::memcpy(s->hd_out, h_out, sizeof(s->hd_out));
+        std::memcpy(s->hd_cnt, h_cnt, sizeof(s->hd_cnt));
+        for (int k = 0; k < 9; ++k) out->H[k] = s->hd_out[kHdHs + k];
+    }
+    // the solution table: slot 0 = E (absent without a model), slots 1..k = the surviving H candidates
+    const int k_surv = out->found_h ? s->hd_cnt[7] : 0;
+    int need = out->found_e ? out->n_inliers_e : 0;
+    need += k_surv * out->n_inliers_h;
+    if (need > out->cap_pts)
+        return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_estimate_possible_relative_poses: point buffer too small", hipSuccess);
+    int off = 0;
+    auto gather = [&](int slot, int src_slot, const int32_t* list, int m) {
+        out->pts_offset[slot] = off;
+        out->pts_count[slot] = m;
+        for (int j = 0; j < m; ++j)
+            std::memcpy(out->pts3d + 3 * (size_t)(off + j), h_pts + 3 * ((size_t)src_slot * n + list[j]), 12);
+        off += m;
+    };
+    if (out->found_e) {
+        out->present[0] = 1;
+        std::memcpy(out->R[0], R_e, sizeof(R_e));
+        std::memcpy(out->t[0], t_e, sizeof(t_e));
+        gather(0, 0, out->inliers_e, out->n_inliers_e);
+    }
+    for (int j = 0; j < k_surv; ++j) {
+        const int c = s->hd_cnt[8 + j], slot = 1 + j;
+        out->present[slot] = 1;
+        out->h_candidate[slot] = c;
+        for (int k = 0; k < 9; ++k) out->R[slot][k] = s->hd_out[kHdR + 9 * c + k];
+        for (int k = 0; k < 3; ++k) {
+            out->t[slot][k] = s->hd_out[kHdTn + 3 * c + k];
+            out->normal[slot][k] = s->hd_out[kHdN + 3 * c + k];
+        }
+        gather(slot, 1 + c, out->inliers_h, out->n_inliers_h);
+    }
+    out->n_slots = 1 + k_surv;
+    // checkEssentialScore / checkHomographyScore; an absent model scores 0 (deviations 9 and 10)
+    std::vector<int32_t> kept((size_t)out->n_inliers_e + out->n_inliers_h + 2);
+    int n_kept_e = 0, n_kept_h = 0;
+    if ((r = mvo_check_init_scores(ctx, pts1, pts2, n, fx, fy, cx, cy, out->found_e ? out->E : nullptr, out->inliers_e,
+                                   out->n_inliers_e, out->found_h ? out->H : nullptr, out->inliers_h, out->n_inliers_h,
+                                   sigma, &out->score_e, &out->score_h, kept.data(), &n_kept_e,
+                                   kept.data() + out->n_inliers_e, &n_kept_h)))
+        return r;
+    out->ratio = out->score_h / (out->score_e + out->score_h);
+    // the choice (motion_estimation.cpp:141-155); a slot that does not exist gives -1 (deviation 11)
+    if (out->ratio > 0.5) {
+        if (k_surv > 0) {
+            int best = 1;
+            double largest = std::fabs(out->normal[1][2]);
+            for (int j = 2; j <= k_surv; ++j) {
+                const double z = std::fabs(out->normal[j][2]);
+                if (z > largest) {
+                    largest = z;
+                    best = j;
+                }
+            }
+            out->best = best;
+        }
+    } else if (out->found_e) {
+        out->best = 0;
+    }
+    if (!motion_cam2_to_cam1)
+        for (int j = 0; j < 5; ++j)
+            if (out->present[j]) inv_rt(out->R[j], out->t[j]);
+    return MVO_OK;
 }
 
 int mvo_retain_good_triangulation(const float* pts3d_in_curr, int n, const double* T_w_c_curr, const double* T_w_c_ref,

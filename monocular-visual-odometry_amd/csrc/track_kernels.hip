@@ -12,9 +12,13 @@
 //   k_h_refine         the DLT on all inliers + LMSolver (10 iterations) that findHomography runs after RANSAC.
 //   k_recover_pose     recoverPose after findEssentialMat (estiMotionByEssential): one lane per (match, combination).
 //   k_init_scores      checkEssentialScore and checkHomographyScore (the E/H choice of the initialisation).
+//   k_h_decompose      decomposeHomographyMat + filterHomographyDecompByVisibleRefpoints after findHomography
+//                      (estiMotionByHomography, removeWrongRtOfHomography): one lane per match, the H inliers vote.
+//   k_init_triangulate doTriangulation of every candidate solution of the initialisation in one launch.
 // The arithmetic lives in pnp_wave.h (wave-level SPMD code); this file binds it to threads and LDS.
 #include "mvo_internal.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 #define PW_FN __device__ __forceinline__
@@ -24,6 +28,7 @@
 #define PW_UNROLL _Pragma("unroll")
 #include "em_wave.h"
 #include "h_wave.h"
+#include "hd_wave.h"
 
 // ------------------------------------------------------------------------------------------------ map in view
 // One workgroup walks the map in chunks of 1024 points and appends the survivors in map order (the reference
@@ -480,6 +485,135 @@ int track_launch_init_scores(mvo_ctx* ctx, const float* d_kp1, const float* d_kp
     ProfScope ps(ctx, "k_init_scores");
     hipLaunchKernelGGL(k_init_scores, dim3(2), dim3(64), 0, ctx->stream, (const float2*)d_kp1, (const float2*)d_kp2,
                        d_lists, n_e, n_h, a, d_scores, d_kept, d_n_kept);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ H decomposition
+// One lane per match i; the lanes of H inliers (mask[i], NULL: every match) test their match against every candidate
+// (filterHomographyDecompByVisibleRefpoints).  Every lane scales H and decomposes it itself (uniform, a few hundred
+// flops and one 3 x 3 Jacobi SVD).  The rejection counts are integer sums (exact in any order): per wave a ballot, per
+// workgroup an add, across workgroups an atomic add; the last workgroup to arrive writes the decomposition, the
+// normalised t and the survivors (count 0, in candidate order).  cnt: kHdCnt ints, out: kHdOut doubles (layouts in
+// mvo_internal.h).
+__global__ __launch_bounds__(256) void k_h_decompose(const float2* __restrict__ kp1, const float2* __restrict__ kp2,
+                                                     const uint8_t* __restrict__ mask, int n,
+                                                     const double* __restrict__ H_raw, TrackCamera cam, int32_t* cnt,
+                                                     double* __restrict__ out) {
+    __shared__ int wave_cnt[4][4];
+    __shared__ int last;
+    const int t = threadIdx.x;
+    double h[9], Hs[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) h[k] = H_raw[k];
+    pw::rp_scale9(h, h[8], Hs);
+    pw::HDecomp d;
+    pw::hd_decompose(Hs, cam.fx, cam.fy, cam.cx, cam.cy, d);
+    const int i = blockIdx.x * 256 + t;
+    bool rej[4] = {false, false, false, false};
+    if (i < n && (!mask || mask[i])) {
+        // pixel2CamNormPlane, a cv::Point2f, then the CV_64FC2 copy the filter works on
+        const double x1 = (float)((kp1[i].x - cam.cx) / cam.fx), y1 = (float)((kp1[i].y - cam.cy) / cam.fy);
+        const double x2 = (float)((kp2[i].x - cam.cx) / cam.fx), y2 = (float)((kp2[i].y - cam.cy) / cam.fy);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) rej[c] = c < d.count && pw::hd_rejects(x1, y1, x2, y2, d.R[c], d.n[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const unsigned long long b = __ballot(rej[c]);
+        if ((t & 63) == 0) wave_cnt[t >> 6][c] = __popcll(b);
+    }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            __hip_atomic_fetch_add(cnt + c, wave_cnt[0][c] + wave_cnt[1][c] + wave_cnt[2][c] + wave_cnt[3][c],
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        last = __hip_atomic_fetch_add(cnt + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last || t != 0) return;
+    __threadfence();
+    int k_surv = 0;
+    for (int c = 0; c < d.count; ++c)
+        if (__hip_atomic_load(cnt + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) cnt[8 + k_surv++] = c;
+    for (int k = 0; k < 9; ++k) {
+        out[kHdHs + k] = Hs[k];
+        out[kHdHn + k] = d.Hn[k];
+    }
+    for (int k = 0; k < 3; ++k) out[kHdW + k] = d.w[k];
+    for (int c = 0; c < 4; ++c) {
+        double tn[3] = {0, 0, 0};
+        if (c < d.count) pw::hd_normalise_t(d.t[c], tn);
+        for (int k = 0; k < 9; ++k) out[kHdR + 9 * c + k] = d.R[c][k];
+        for (int k = 0; k < 3; ++k) {
+            out[kHdT + 3 * c + k] = d.t[c][k];
+            out[kHdN + 3 * c + k] = d.n[c][k];
+            out[kHdTn + 3 * c + k] = tn[k];
+        }
+    }
+    cnt[5] = d.count;
+    cnt[6] = d.branch;
+    cnt[7] = k_surv;
+}
+
+int track_launch_h_decompose(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, const uint8_t* d_mask, int n,
+                             const double* d_H, const TrackCamera& cam, int32_t* d_cnt, double* d_out) {
+    MVO_HIP(hipMemsetAsync(d_cnt, 0, 5 * sizeof(int32_t), ctx->stream));
+    ProfScope ps(ctx, "k_h_decompose");
+    hipLaunchKernelGGL(k_h_decompose, dim3((std::max(n, 1) + 255) / 256), dim3(256), 0, ctx->stream,
+                       (const float2*)d_kp1, (const float2*)d_kp2, d_mask, n, d_H, cam, d_cnt, d_out);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ init triangulation
+// doTriangulation of every solution of helperEstimatePossibleRelativePosesByEpipolarGeometry: blockIdx.y = slot (0: the
+// E motion R, t of k_recover_pose's out; 1..4: the H candidates of k_h_decompose, R and the normalised t), one lane per
+// match; the lanes of the slot's inliers (mask, NULL: every match) write pts[slot][i] (the point in camera 1, as
+// pw::triangulate_match gives it).  e_out == NULL: no E slot; h_out == NULL: no H slots; H slots past the candidate
+// count are skipped.
+__global__ __launch_bounds__(256) void k_init_triangulate(const float2* __restrict__ kp1, const float2* __restrict__ kp2,
+                                                          int n, TrackCamera cam, const double* __restrict__ e_out,
+                                                          const uint8_t* __restrict__ e_mask,
+                                                          const double* __restrict__ h_out,
+                                                          const int32_t* __restrict__ h_cnt,
+                                                          const uint8_t* __restrict__ h_mask, float* __restrict__ pts) {
+    const int slot = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double R[9], tv[3];
+    if (slot == 0) {
+        if (!e_out || (e_mask && !e_mask[i])) return;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = e_out[9 + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tv[k] = e_out[18 + k];
+    } else {
+        const int c = slot - 1;
+        if (!h_out || c >= h_cnt[5] || (h_mask && !h_mask[i])) return;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) R[k] = h_out[kHdR + 9 * c + k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tv[k] = h_out[kHdTn + 3 * c + k];
+    }
+    const pw::Camera c{cam.fx, cam.fy, cam.cx, cam.cy};
+    const float a[2] = {kp1[i].x, kp1[i].y}, b[2] = {kp2[i].x, kp2[i].y};
+    float pp[3], pc[3];
+    pw::triangulate_match(a, b, c, R, tv, pp, pc);
+    float* o = pts + 3 * ((size_t)slot * n + i);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) o[r] = pp[r];
+}
+
+int track_launch_init_triangulate(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, int n, const TrackCamera& cam,
+                                  const double* d_e_out, const uint8_t* d_e_mask, const double* d_h_out,
+                                  const int32_t* d_h_cnt, const uint8_t* d_h_mask, float* d_pts) {
+    if (n == 0) return MVO_OK;
+    ProfScope ps(ctx, "k_init_triangulate");
+    hipLaunchKernelGGL(k_init_triangulate, dim3((n + 255) / 256, 5), dim3(256), 0, ctx->stream, (const float2*)d_kp1,
+                       (const float2*)d_kp2, n, cam, d_e_out, d_e_mask, d_h_out, d_h_cnt, d_h_mask, d_pts);
     MVO_HIP(hipGetLastError());
     return MVO_OK;
 }

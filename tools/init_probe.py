@@ -3,8 +3,11 @@ matches with 0 / 50 % wrong matches, beside the sequential CPU restatement of th
 --essential: the same for mvo_esti_motion_by_essential (thick scene) beside mvo_find_essential_inliers on the same matches
 (the difference is what recoverPose adds), and mvo_check_init_scores on both models, beside the restatement
 (tests/init_motion_restatement.cpp; its RANSAC stage is the CPU oracle's).
+--poses: mvo_estimate_possible_relative_poses (planar scene) beside the sum of the separate mvo_esti_motion_by_essential +
+mvo_find_homography + mvo_check_init_scores calls on the same matches, and beside the sequential restatement
+(tests/pose_restate.py; its E RANSAC stage is the CPU oracle's).
 Per-kernel device times: run it under rocprofv3 --kernel-trace --stats.
-Usage: python tools/init_probe.py [--essential] [--reps 50] [--out FILE]"""
+Usage: python tools/init_probe.py [--essential | --poses] [--reps 50] [--out FILE]"""
 import argparse
 import json
 import os
@@ -19,6 +22,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as graft  # noqa: E402
 import h_restate as HR  # noqa: E402
 import init_restate as IR  # noqa: E402
+import pose_restate as PR  # noqa: E402
 
 
 def timed(fn, reps):
@@ -37,6 +41,7 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None)
     ap.add_argument("--essential", action="store_true")
+    ap.add_argument("--poses", action="store_true")
     a = ap.parse_args()
     mvo = graft.load_package()
     ctx = mvo.Context(0)
@@ -64,7 +69,30 @@ def main():
                                  scores_ms_median=sc_med, scores_ms_min=sc_min, cpu_esti_motion_ms_median=cpu_rp,
                                  cpu_scores_ms_median=cpu_sc))
                 print(json.dumps(rows[-1]), flush=True)
-    for n in (() if a.essential else (500, 1000, 2000)):
+    if a.poses:
+        O = graft.load_oracle()
+        O.build()
+        PRR = PR.Restatement()
+        for n in (500, 1000, 2000):
+            for frac in (0.0, 0.5):
+                pr = HR.two_view(n, 300 + n, planar=True, noise=0.5, outlier_frac=frac)
+                s, d, K = pr["src"], pr["dst"], IR.kdict(pr["K"])
+                g = ctx.estimate_possible_relative_poses(s, d, K)
+
+                def separate():
+                    e = ctx.esti_motion_by_essential(s, d, K)
+                    h = ctx.find_homography(s, d)
+                    ctx.check_init_scores(s, d, K, e["E"], e["inliers"], IR.scale_by_22(h["H"]), h["inliers"])
+
+                po_med, po_min = timed(lambda: ctx.estimate_possible_relative_poses(s, d, K), a.reps)
+                sep_med, sep_min = timed(separate, a.reps)
+                cpu_med, _ = timed(lambda: PRR.estimate_possible_relative_poses(O, s, d, pr["K"]), max(5, a.reps // 10))
+                rows.append(dict(n=n, outliers=frac, n_inl_e=len(g["inliers_e"]), n_inl_h=len(g["inliers_h"]),
+                                 n_slots=len(g["solutions"]), best=g["best"], ratio=g["ratio"], poses_ms_median=po_med,
+                                 poses_ms_min=po_min, separate_ms_median=sep_med, separate_ms_min=sep_min,
+                                 cpu_restatement_ms_median=cpu_med))
+                print(json.dumps(rows[-1]), flush=True)
+    for n in (() if a.essential or a.poses else (500, 1000, 2000)):
         for frac in (0.0, 0.5):
             pr = HR.two_view(n, 100 + n, planar=True, noise=0.5, outlier_frac=frac)
             s, d = pr["src"], pr["dst"]
