@@ -379,6 +379,49 @@ int mvo_estimate_possible_relative_poses(mvo_ctx* ctx, const float* pts1, const 
                                          double fy, double cx, double cy, double prob, double threshold,
                                          double h_threshold, double h_confidence, double sigma,
                                          int motion_cam2_to_cam1, mvo_init_poses* out);
+/* Parameters of the finish of the monocular initialisation (config/config.yaml:105-113): min_triang_angle and
+ * max_ratio_to_median of retainGoodTriangulationResult_, assumed_mean_pts_depth_during_vo_init, and the three
+ * thresholds of isVoGoodToInit_.  The reference's values: 1.0, 20, 0.8, 15, 50, 2.0. */
+typedef struct {
+    double min_triang_angle, max_ratio_to_median, assumed_mean_depth;
+    int min_inlier_matches;
+    double min_pixel_dist, min_median_triangulation_angle;
+} mvo_init_params;
+/* Result of mvo_init_two_view.  The caller sets the three buffers and cap (>= n); the call fills the rest.
+ * matches_for_3d: curr_->inliers_matches_for_3d_ as indices into the input matches; pts3d_in_curr (x, y, z per
+ * point): curr_->inliers_pts3d_; angles: curr_->triangulation_angles_of_inliers_ (degrees), n_kept entries each.
+ * slot: the chosen solution (poses->best); n_slot_inliers: the length of its inlier list; scaled: 1 when the depth
+ * scaling ran (n_kept >= 20), else 0 with mean_depth = scale = 0 and points, t and T_w_c unscaled (vo.cpp:94-99).
+ * R, t: the motion of the chosen slot, t times scale when scaled; T_w_c: curr_->T_w_c_.  mean_pixel_dist: the mean
+ * of criteria_1 (NaN when nothing is kept); mean / median / min / max_angle: what isVoGoodToInit_ prints (0 when
+ * nothing is kept); criteria[3] and good: its three tests and their conjunction. */
+typedef struct {
+    int32_t* matches_for_3d;
+    float* pts3d_in_curr;
+    double* angles;
+    int cap;
+    int slot, n_slot_inliers, n_kept, scaled;
+    double R[9], t[3], T_w_c[16], mean_depth, scale;
+    double mean_pixel_dist, mean_angle, median_angle, min_angle, max_angle;
+    int criteria[3], good;
+} mvo_init_result;
+/* The DOING_INITIALIZATION step after the matching: VisualOdometry::estimateMotionAnd3DPoints_ (src/vo/vo.cpp:53-110)
+ * and VisualOdometry::isVoGoodToInit_ (vo.cpp:112-170) as vo_addFrame.cpp:50-56 calls them.  Runs
+ * mvo_estimate_possible_relative_poses with motion_cam2_to_cam1 = 1 (vo.cpp:66; poses receives exactly that call's
+ * outputs), then on slot poses->best: basics::transCoord of the slot's points into the current camera, the pose
+ * T = T_w_c_ref * [R t; 0 1]^-1 (the LU of mvo_invert_pose; the product summed k = 0..3 in order),
+ * retainGoodTriangulationResult_ (vo.cpp:181-244, the rule of mvo_retain_good_triangulation on cosines computed by
+ * the device: acos, the sort for the median and the keep list are host-side), the N < 20 early return, the depth
+ * scaling to assumed_mean_depth with the pose recomputed from the scaled t, and the three criteria, which are
+ * evaluated in either case.  T_w_c_ref: ref_->T_w_c_, row-major 4 x 4.  A NaN angle (a cosine outside [-1, 1] by
+ * rounding, or a zero ray) is treated exactly as mvo_retain_good_triangulation treats it: both comparisons of the
+ * keep rule are false for it, so the point is kept, and it takes part in the sort for the median as it is.
+ * best == -1 (deviations 9-11; the reference would index list_R[-1]): nothing is launched,
+ * slot = -1, n_kept = 0, all criteria and good are 0, T_w_c = T_w_c_ref, and the call returns MVO_OK (deviation 12). */
+int mvo_init_two_view(mvo_ctx* ctx, const float* pts1, const float* pts2, int n, double fx, double fy, double cx,
+                      double cy, double prob, double threshold, double h_threshold, double h_confidence, double sigma,
+                      const double* T_w_c_ref, const mvo_init_params* params, mvo_init_poses* poses,
+                      mvo_init_result* out);
 /* VisualOdometry::retainGoodTriangulationResult_ (src/vo/vo.cpp:181-244), host-side (acos + a sort for the
  * median): keep[i] lists the points whose triangulation angle (degrees) is >= min_triang_angle and at most
  * max_ratio_to_median times the median; angles (n, may be NULL) receives every angle. */
@@ -479,6 +522,11 @@ int mvo_debug_get_recover_pose(mvo_ctx* ctx, int32_t* good, int32_t* chosen, dou
  * the number of candidates: 0 when there was no H, 1 for the rotation-only branch, else 4. */
 int mvo_debug_get_homography_decomposition(mvo_ctx* ctx, double* Hn, double* w, int32_t* branch, double* Rs,
                                            double* ts, double* normals, int32_t* rejected);
+/* Record of the last mvo_init_two_view on this ctx, what k_init_finish wrote for every entry of the chosen slot's
+ * inlier list, in list order: p_curr (n x 3 float, before the keep rule and the scaling), cosang (the cosine of the
+ * triangulation angle) and pixdist (basics::calcDist of the match's two pixels).  Any buffer may be NULL; *n receives
+ * the number of entries (0 after a call with best == -1). */
+int mvo_debug_get_init_finish(mvo_ctx* ctx, float* p_curr, double* cosang, double* pixdist, int cap, int* n);
 
 #ifdef __cplusplus
 }

@@ -70,6 +70,23 @@ class InitPoses(C.Structure):
                 ("score_e", C.c_double), ("score_h", C.c_double), ("ratio", C.c_double), ("best", C.c_int)]
 
 
+class InitParams(C.Structure):
+    """mvo_init_params (include/mvo_hip.h)."""
+    _fields_ = [("min_triang_angle", C.c_double), ("max_ratio_to_median", C.c_double), ("assumed_mean_depth", C.c_double),
+                ("min_inlier_matches", C.c_int), ("min_pixel_dist", C.c_double),
+                ("min_median_triangulation_angle", C.c_double)]
+
+
+class InitResult(C.Structure):
+    """mvo_init_result (include/mvo_hip.h)."""
+    _fields_ = [("matches_for_3d", C.c_void_p), ("pts3d_in_curr", C.c_void_p), ("angles", C.c_void_p), ("cap", C.c_int),
+                ("slot", C.c_int), ("n_slot_inliers", C.c_int), ("n_kept", C.c_int), ("scaled", C.c_int),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("T_w_c", C.c_double * 16), ("mean_depth", C.c_double),
+                ("scale", C.c_double), ("mean_pixel_dist", C.c_double), ("mean_angle", C.c_double),
+                ("median_angle", C.c_double), ("min_angle", C.c_double), ("max_angle", C.c_double),
+                ("criteria", C.c_int * 3), ("good", C.c_int)]
+
+
 _lib = None
 
 
@@ -561,6 +578,10 @@ class Context:
             self.h, _p(a), _p(b), n, C.c_double(K["fx"]), C.c_double(K["fy"]), C.c_double(K["cx"]), C.c_double(K["cy"]),
             C.c_double(prob), C.c_double(threshold), C.c_double(h_threshold), C.c_double(h_confidence),
             C.c_double(sigma), int(bool(motion_cam2_to_cam1)), C.byref(o)))
+        return self._poses_dict(o, ie, ih, pts)
+
+    @staticmethod
+    def _poses_dict(o, ie, ih, pts):
         ine, inh = ie[:o.n_inliers_e].copy(), ih[:o.n_inliers_h].copy()
         sols = []
         for s in range(o.n_slots):
@@ -575,6 +596,52 @@ class Context:
         return dict(best=int(o.best), ratio=o.ratio, score_e=o.score_e, score_h=o.score_h,
                     E=np.array(o.E).reshape(3, 3) if o.found_e else None, H=np.array(o.H).reshape(3, 3) if o.found_h else None,
                     inliers_e=ine, inliers_h=inh, solutions=sols)
+
+    def init_two_view(self, kp1, kp2, K, T_w_c_ref=None, prob=0.999, threshold=1.0, h_threshold=3.0, h_confidence=0.995,
+                      sigma=1.0, min_triang_angle=1.0, max_ratio_to_median=20.0, assumed_mean_depth=0.8,
+                      min_inlier_matches=15, min_pixel_dist=50.0, min_median_triangulation_angle=2.0):
+        """VisualOdometry::estimateMotionAnd3DPoints_ + isVoGoodToInit_ (vo.cpp:53-170; defaults of config.yaml:101-113)
+        -> dict(poses (what estimate_possible_relative_poses returns), slot, n_slot_inliers, n_kept, scaled,
+        matches_for_3d (indices into the matches), pts3d_in_curr, angles, R, t, T_w_c, mean_depth, scale,
+        mean_pixel_dist, mean_angle, median_angle, min_angle, max_angle, criteria (3 bools), good).  T_w_c_ref: the
+        pose of the first keyframe (identity by default)."""
+        a = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
+        assert len(a) == len(b)
+        n = len(a)
+        Tr = np.ascontiguousarray(np.eye(4) if T_w_c_ref is None else T_w_c_ref, np.float64).reshape(4, 4)
+        ie, ih = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        pts = np.zeros((max(5 * n, 1), 3), np.float32)
+        o = InitPoses()
+        o.inliers_e, o.inliers_h, o.cap_inliers = _p(ie), _p(ih), len(ie)
+        o.pts3d, o.cap_pts = _p(pts), len(pts)
+        m3d, p3d, ang = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1))
+        res = InitResult()
+        res.matches_for_3d, res.pts3d_in_curr, res.angles, res.cap = _p(m3d), _p(p3d), _p(ang), len(m3d)
+        prm = InitParams(min_triang_angle, max_ratio_to_median, assumed_mean_depth, int(min_inlier_matches),
+                         min_pixel_dist, min_median_triangulation_angle)
+        self._chk(self.lib.mvo_init_two_view(
+            self.h, _p(a), _p(b), n, C.c_double(K["fx"]), C.c_double(K["fy"]), C.c_double(K["cx"]), C.c_double(K["cy"]),
+            C.c_double(prob), C.c_double(threshold), C.c_double(h_threshold), C.c_double(h_confidence),
+            C.c_double(sigma), _p(Tr), C.byref(prm), C.byref(o), C.byref(res)))
+        k = res.n_kept
+        return dict(poses=self._poses_dict(o, ie, ih, pts), slot=int(res.slot), n_slot_inliers=int(res.n_slot_inliers),
+                    n_kept=int(k), scaled=bool(res.scaled), matches_for_3d=m3d[:k].copy(), pts3d_in_curr=p3d[:k].copy(),
+                    angles=ang[:k].copy(), R=np.array(res.R).reshape(3, 3), t=np.array(res.t),
+                    T_w_c=np.array(res.T_w_c).reshape(4, 4), mean_depth=res.mean_depth, scale=res.scale,
+                    mean_pixel_dist=res.mean_pixel_dist, mean_angle=res.mean_angle, median_angle=res.median_angle,
+                    min_angle=res.min_angle, max_angle=res.max_angle, criteria=[bool(c) for c in res.criteria],
+                    good=bool(res.good))
+
+    def debug_init_finish(self):
+        """Record of the last init_two_view: what k_init_finish wrote per entry of the chosen slot's inlier list ->
+        dict(p_curr (m x 3 f32, unscaled), cosang, pixdist (m f64))."""
+        n = C.c_int()
+        self._chk(self.lib.mvo_debug_get_init_finish(self.h, None, None, None, 0, C.byref(n)))
+        m = n.value
+        pc, cs, pd = np.zeros((max(m, 1), 3), np.float32), np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        self._chk(self.lib.mvo_debug_get_init_finish(self.h, _p(pc), _p(cs), _p(pd), len(cs), C.byref(n)))
+        return dict(p_curr=pc[:m].copy(), cosang=cs[:m].copy(), pixdist=pd[:m].copy())
 
     def debug_homography(self):
         counts = np.zeros(2000, np.int32)

@@ -229,6 +229,10 @@ struct mvo_ctx {
     int m_cap_q = 0, m_cap_t = 0;
     // --- tracking rows
     mvo_track_state* track = nullptr;
+    // record of the last mvo_init_two_view (init_host.cpp; mvo_debug_get_init_finish)
+    bool init_called = false;
+    std::vector<float> init_p_curr;
+    std::vector<double> init_cosang, init_pixdist;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -310,11 +314,25 @@ int track_launch_h_decompose(mvo_ctx* ctx, const float* d_kp1, const float* d_kp
 int track_launch_init_triangulate(mvo_ctx* ctx, const float* d_kp1, const float* d_kp2, int n, const TrackCamera& cam,
                                   const double* d_e_out, const uint8_t* d_e_mask, const double* d_h_out,
                                   const int32_t* d_h_cnt, const uint8_t* d_h_mask, float* d_pts);
+int track_launch_init_finish(mvo_ctx* ctx, const float* d_pts, const int32_t* d_list, int m, const double* d_R,
+                             const double* d_t, const float* d_kp1, const float* d_kp2, const double* T_w_c_curr,
+                             const double* T_w_c_ref, float* d_p_curr, double* d_cosang, double* d_pixdist);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence
 // track_host.cpp
 void track_release(mvo_ctx* ctx);
+// What the last mvo_estimate_possible_relative_poses(n matches) of this ctx left on the device, for the finish of the
+// initialisation (init_host.cpp): the matched pixels, the E list followed by the H list, k_recover_pose's and
+// k_h_decompose's outputs and k_init_triangulate's [5][n] points; and out, room for k_init_finish's results on m
+// list entries (28 m bytes).
+struct TrackInitView {
+    const float *kp1, *kp2, *pts;
+    const int32_t* lists;
+    const double *e_out, *h_out;
+    uint8_t* out;
+};
+int track_init_view(mvo_ctx* ctx, int n, int m, TrackInitView* v);
 // ba_host.cpp (planning, pooled workspaces, launch service) + ba_kernels.hip (k_ba_lm)
 struct mvo_ba_handle;
 int ba_solve_device(mvo_ctx* ctx, mvo_ba_problem* p, mvo_ba_stats* st);

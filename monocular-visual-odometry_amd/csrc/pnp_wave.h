@@ -853,6 +853,16 @@ PW_FN int score_model(HypLds& s, const float* p3, const float* p2, int n, const 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// basics::transCoord (opencv_funcs.cpp): (float)(R p + t), every entry summed k = 0..2 in order, then + t.
+PW_FN void trans_coord(const float (&p)[3], const double (&R)[9], const double (&t)[3], float (&out)[3]) {
+    PW_UNROLL
+    for (int r = 0; r < 3; r++) {
+        double s = R[3 * r] * (double)p[0] + R[3 * r + 1] * (double)p[1];
+        s = s + R[3 * r + 2] * (double)p[2];
+        out[r] = (float)(s + t[r]);
+    }
+}
+
 // geometry::helperTriangulatePoints for ONE match (motion_estimation.cpp:214-247): pixel2CamNormPlane on both
 // pixels, cv::triangulatePoints with P1 = [I | 0], P2 = [R | t] (the 4x4 DLT system, right singular vector of the
 // smallest singular value, stored as float like OpenCV does for Point2f input), division by w in float, then
@@ -884,12 +894,7 @@ PW_FN void triangulate_match(const float* kp1, const float* kp2, const Camera& c
     const float X[4] = {(float)Vt[3][0], (float)Vt[3][1], (float)Vt[3][2], (float)Vt[3][3]};
     PW_UNROLL
     for (int r = 0; r < 3; r++) p_prev[r] = X[r] / X[3];
-    PW_UNROLL
-    for (int r = 0; r < 3; r++) {
-        double s = R[3 * r] * (double)p_prev[0] + R[3 * r + 1] * (double)p_prev[1];
-        s = s + R[3 * r + 2] * (double)p_prev[2];
-        p_curr[r] = (float)(s + t[r]);
-    }
+    trans_coord(p_prev, R, t, p_curr);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -74,6 +74,8 @@ struct mvo_track_state {
     int32_t hd_cnt[kHdCnt] = {};
     float* d_ip_pts = nullptr;
     size_t cap_ip_pts = 0;
+    uint8_t* d_fin = nullptr;  // k_init_finish's results
+    size_t cap_fin = 0;
     // map points in view
     uint8_t* d_view_desc = nullptr;
     int32_t* d_view_n = nullptr;
@@ -497,8 +499,29 @@ void track_release(mvo_ctx* ctx) {
     free_dev(s->d_hd_out);
     free_dev(s->d_hd_cnt);
     free_dev(s->d_ip_pts);
+    free_dev(s->d_fin);
     delete s;
     ctx->track = nullptr;
+}
+
+int track_init_view(mvo_ctx* ctx, int n, int m, TrackInitView* v) {
+    mvo_track_state* s = state(ctx);
+    const size_t bytes = (size_t)m * 28;
+    if (bytes > s->cap_fin) {
+        free_dev(s->d_fin);
+        s->cap_fin = 0;
+        const size_t c = std::max<size_t>(1 << 16, bytes + bytes / 2);
+        MVO_HIP(hipMalloc((void**)&s->d_fin, c));
+        s->cap_fin = c;
+    }
+    v->out = s->d_fin;
+    v->kp1 = reinterpret_cast<const float*>(s->d_sc_in);
+    v->kp2 = reinterpret_cast<const float*>(s->d_sc_in + (size_t)n * 8);
+    v->lists = reinterpret_cast<const int32_t*>(s->d_sc_in + (size_t)n * 16);
+    v->pts = s->d_ip_pts;
+    v->e_out = s->d_rp_out;
+    v->h_out = s->d_hd_out;
+    return MVO_OK;
 }
 
 extern "C" {

@@ -15,6 +15,8 @@
 //   k_h_decompose      decomposeHomographyMat + filterHomographyDecompByVisibleRefpoints after findHomography
 //                      (estiMotionByHomography, removeWrongRtOfHomography): one lane per match, the H inliers vote.
 //   k_init_triangulate doTriangulation of every candidate solution of the initialisation in one launch.
+//   k_init_finish      the chosen solution's points in the current camera, the cosine of every triangulation angle and
+//                      the pixel distance of every match (estimateMotionAnd3DPoints_, isVoGoodToInit_; init_wave.h).
 // The arithmetic lives in pnp_wave.h (wave-level SPMD code); this file binds it to threads and LDS.
 #include "mvo_internal.h"
 
@@ -29,6 +31,7 @@
 #include "em_wave.h"
 #include "h_wave.h"
 #include "hd_wave.h"
+#include "init_wave.h"
 
 // ------------------------------------------------------------------------------------------------ map in view
 // One workgroup walks the map in chunks of 1024 points and appends the survivors in map order (the reference
@@ -614,6 +617,50 @@ int track_launch_init_triangulate(mvo_ctx* ctx, const float* d_kp1, const float*
     ProfScope ps(ctx, "k_init_triangulate");
     hipLaunchKernelGGL(k_init_triangulate, dim3((n + 255) / 256, 5), dim3(256), 0, ctx->stream, (const float2*)d_kp1,
                        (const float2*)d_kp2, n, cam, d_e_out, d_e_mask, d_h_out, d_h_cnt, d_h_mask, d_pts);
+    MVO_HIP(hipGetLastError());
+    return MVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ init finish
+// The chosen solution of the initialisation, one lane per entry of its inlier list (list[j] = index of the match):
+// pts = that solution's row of k_init_triangulate's output (indexed by match), R / t = where k_recover_pose or
+// k_h_decompose left the solution's motion.  p_curr: m x 3 float, cosang and pixdist: m doubles (pw::init_finish_point).
+__global__ __launch_bounds__(256) void k_init_finish(const float* __restrict__ pts, const int32_t* __restrict__ list, int m,
+                                                      const double* __restrict__ R_dev, const double* __restrict__ t_dev,
+                                                      const float2* __restrict__ kp1, const float2* __restrict__ kp2,
+                                                      pw::InitFinishPoses T, float* __restrict__ p_curr,
+                                                      double* __restrict__ cosang, double* __restrict__ pixdist) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    double R[9], tv[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R[k] = R_dev[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tv[k] = t_dev[k];
+    const int i = list[j];
+    const float p1[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+    const float a[2] = {kp1[i].x, kp1[i].y}, b[2] = {kp2[i].x, kp2[i].y};
+    float pc[3];
+    double c, d;
+    pw::init_finish_point(p1, R, tv, T, a, b, pc, &c, &d);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) p_curr[3 * (size_t)j + r] = pc[r];
+    cosang[j] = c;
+    pixdist[j] = d;
+}
+
+int track_launch_init_finish(mvo_ctx* ctx, const float* d_pts, const int32_t* d_list, int m, const double* d_R,
+                             const double* d_t, const float* d_kp1, const float* d_kp2, const double* T_w_c_curr,
+                             const double* T_w_c_ref, float* d_p_curr, double* d_cosang, double* d_pixdist) {
+    if (m == 0) return MVO_OK;
+    pw::InitFinishPoses T;
+    for (int k = 0; k < 16; ++k) {
+        T.curr[k] = T_w_c_curr[k];
+        T.ref[k] = T_w_c_ref[k];
+    }
+    ProfScope ps(ctx, "k_init_finish");
+    hipLaunchKernelGGL(k_init_finish, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, d_pts, d_list, m, d_R, d_t,
+                       (const float2*)d_kp1, (const float2*)d_kp2, T, d_p_curr, d_cosang, d_pixdist);
     MVO_HIP(hipGetLastError());
     return MVO_OK;
 }

@@ -6,8 +6,10 @@ matches with 0 / 50 % wrong matches, beside the sequential CPU restatement of th
 --poses: mvo_estimate_possible_relative_poses (planar scene) beside the sum of the separate mvo_esti_motion_by_essential +
 mvo_find_homography + mvo_check_init_scores calls on the same matches, and beside the sequential restatement
 (tests/pose_restate.py; its E RANSAC stage is the CPU oracle's).
+--finish: mvo_init_two_view (thick scene, the E slot is chosen) beside mvo_estimate_possible_relative_poses on the same matches
+in the same run: the difference is what the finish adds (k_init_finish, its read-back and the host tail).
 Per-kernel device times: run it under rocprofv3 --kernel-trace --stats.
-Usage: python tools/init_probe.py [--essential | --poses] [--reps 50] [--out FILE]"""
+Usage: python tools/init_probe.py [--essential | --poses | --finish] [--reps 50] [--out FILE]"""
 import argparse
 import json
 import os
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--essential", action="store_true")
     ap.add_argument("--poses", action="store_true")
+    ap.add_argument("--finish", action="store_true")
     a = ap.parse_args()
     mvo = graft.load_package()
     ctx = mvo.Context(0)
@@ -92,7 +95,19 @@ def main():
                                  poses_ms_min=po_min, separate_ms_median=sep_med, separate_ms_min=sep_min,
                                  cpu_restatement_ms_median=cpu_med))
                 print(json.dumps(rows[-1]), flush=True)
-    for n in (() if a.essential or a.poses else (500, 1000, 2000)):
+    if a.finish:
+        for n in (500, 1000, 2000):
+            for frac in (0.0, 0.5):
+                pr = HR.two_view(n, 400 + n, planar=False, noise=0.5, outlier_frac=frac)
+                s, d, K = pr["src"], pr["dst"], IR.kdict(pr["K"])
+                g = ctx.init_two_view(s, d, K)
+                po_med, po_min = timed(lambda: ctx.estimate_possible_relative_poses(s, d, K), a.reps)
+                in_med, in_min = timed(lambda: ctx.init_two_view(s, d, K), a.reps)
+                rows.append(dict(n=n, outliers=frac, slot=g["slot"], n_slot_inliers=g["n_slot_inliers"], n_kept=g["n_kept"],
+                                 good=g["good"], poses_ms_median=po_med, poses_ms_min=po_min, init_two_view_ms_median=in_med,
+                                 init_two_view_ms_min=in_min, finish_adds_ms_median=in_med - po_med))
+                print(json.dumps(rows[-1]), flush=True)
+    for n in (() if a.essential or a.poses or a.finish else (500, 1000, 2000)):
         for frac in (0.0, 0.5):
             pr = HR.two_view(n, 100 + n, planar=True, noise=0.5, outlier_frac=frac)
             s, d = pr["src"], pr["dst"]
