@@ -6,14 +6,23 @@
 // keyframes the epipolar inlier filter + triangulation + culling (my_slam/vo/tracking_loop.h = the DOING_TRACKING branch of
 // VisualOdometry::addFrame, vo_addFrame.cpp:70-124).
 //
-// What is NOT here is the reference's INITIALIZATION state (essential / homography model selection, recoverPose --
-// SURVEY.md section 2 marks it out of scope): the map is seeded instead from two frames whose poses are taken from the
-// dataset's ground-truth trajectory (`true_traj_filename`, config.yaml:24; keys `init_keyframe_0/1` pick the frames,
-// default 0 and 5): their matches are filtered and triangulated exactly as a keyframe insertion does it
-// (vo_addFrame.cpp:96-118), which also fixes the scale.  From then on nothing of the ground truth is used.
+// Two ways to start, chosen by the key `init_from_images` (0 / 1, default 0):
+//   1  from the images alone, like the reference: my_slam::vo::VisualOdometry (my_slam/vo/vo.h) takes every frame;
+//      the first one is the first keyframe at the identity, the following ones go through the monocular initialisation
+//      (matchFeatures with the first keyframe, mvo_init_two_view, isVoGoodToInit_) until one passes and fills the map,
+//      the rest is tracked.  The loop is run_vo.cpp:110-148: createFrame -> addFrame -> pose history -> clearNoUsed().
+//      Frames the initialisation rejects carry the first keyframe's pose, the identity.  `true_traj_filename` and
+//      `init_keyframe_0/1` are neither needed nor read.  The program says `initialised at frame N`, or in its last line
+//      that it never initialised (the trajectory is written and the exit status is 0 either way, as in the reference).
+//   0  the map is seeded from two frames whose poses are taken from the dataset's ground-truth trajectory
+//      (`true_traj_filename`, config.yaml:24; keys `init_keyframe_0/1` pick the frames, default 0 and 5): their matches
+//      are filtered and triangulated exactly as a keyframe insertion does it (vo_addFrame.cpp:96-118), which also fixes
+//      the scale.  From then on nothing of the ground truth is used.
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
-// iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py, which composes the same run from
-// the oracle and compares stage by stage.
+// iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
+// which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
+// frame adds MREF, INIT (int32 slot, n_slot_inliers, n_kept, scaled, criteria[3], good; then f64 mean_depth, scale,
+// median_angle, mean_pixel_dist), IREF, I3DM, I3DP, and the frame that initialises MIDS / MPOS.
 //   run_vo <config.yaml>
 #include <algorithm>
 #include <cstdio>
@@ -21,7 +30,12 @@
 
 #include "my_slam/basics/image_io.h"
 #include "my_slam/vo/tracking_loop.h"
+#include "my_slam/vo/vo.h"
 #include "my_slam/vo/vo_io.h"
+
+// Bound weakly: a build of the library without the host side of the initialisation (the emulated libmvo_sim.so of tests/sim)
+// still serves the seeded start; asking such a library for `init_from_images` is an error, not a fall-back.
+#pragma weak mvo_init_two_view
 
 using namespace my_slam;
 
@@ -50,9 +64,9 @@ struct FrameLog {
         vec("KPTS", fr->keypoints_);
         put("DESC", fr->descriptors_.data, (size_t)fr->descriptors_.rows * 32);
     }
-    void tracked(const vo::TrackingState& st, const vo::Frame::Ptr& fr, bool good, bool is_keyframe) {
+    void tracked(const vo::MapOnDevice& dev_map, const vo::Frame::Ptr& fr, bool good, bool is_keyframe) {
         vector<int> order;
-        for (const vo::MapPoint::Ptr& p : st.dev_map_.order()) order.push_back(p->id_);
+        for (const vo::MapPoint::Ptr& p : dev_map.order()) order.push_back(p->id_);
         vec("MORD", order);  // iteration order of Map::map_points_ when the frame looked at the map
         vec("MMAP", fr->matches_with_map_);  // the PnP inliers' matches (vo.cpp:336-349)
         const int flags[2] = {good ? 1 : 0, is_keyframe ? 1 : 0};
@@ -60,9 +74,26 @@ struct FrameLog {
     }
     void keyframe(const vo::Map::Ptr& map, const vo::Frame::Ptr& fr) {
         vec("MREF", fr->matches_with_ref_);
+        triangulated(fr);
+        mapAfter(map);
+    }
+    void initialization(const vo::Map::Ptr& map, const vo::Frame::Ptr& fr, const vo::InitReport& rep, bool initialized) {
+        vec("MREF", fr->matches_with_ref_);  // the matches with the first keyframe
+        const int head[8] = {rep.slot, rep.n_slot_inliers, rep.n_kept, rep.scaled, rep.criteria[0], rep.criteria[1], rep.criteria[2], rep.good};
+        const double tail[4] = {rep.mean_depth, rep.scale, rep.median_angle, rep.mean_pixel_dist};
+        unsigned char rec[sizeof head + sizeof tail];
+        std::memcpy(rec, head, sizeof head);
+        std::memcpy(rec + sizeof head, tail, sizeof tail);
+        put("INIT", rec, sizeof rec);
+        triangulated(fr);
+        if (initialized) mapAfter(map);
+    }
+    void triangulated(const vo::Frame::Ptr& fr) {
         vec("IREF", fr->inliers_matches_with_ref_);
         vec("I3DM", fr->inliers_matches_for_3d_);
         vec("I3DP", fr->inliers_pts3d_);
+    }
+    void mapAfter(const vo::Map::Ptr& map) {
         vector<int> ids;
         vector<float> pos;
         for (auto& kv : map->map_points_) {
@@ -80,6 +111,51 @@ struct FrameLog {
         put("POSE", T, sizeof T);
     }
 };
+
+// `init_from_images: 1`: the reference's loop (run_vo.cpp:110-148) around VisualOdometry::addFrame
+int runFromImages(const vector<string>& image_paths, const cv::Mat& K, int n_proc, FrameLog& log) {
+    if (!mvo_init_two_view) throw std::runtime_error("init_from_images: this libmvo_hip.so has no mvo_init_two_view");
+    vo::VisualOdometry::Ptr odometry(new vo::VisualOdometry(K));
+    vector<cv::Mat> cam_pose_history;
+    int n_tracked = 0, n_lost = 0, n_keyframes = 0, n_rejected = 0, init_frame = -1;
+    for (int img_id = 0; img_id < n_proc; img_id++) {
+        cv::Mat rgb_img = basics::imread(image_paths[img_id]);
+        if (rgb_img.data == nullptr) {
+            printf("The image file %s is empty. Finished.\n", image_paths[img_id].c_str());
+            break;
+        }
+        vo::Frame::Ptr frame = vo::Frame::createFrame(rgb_img);
+        odometry->addFrame(frame);
+        const vo::VisualOdometry::LastFrame& did = odometry->last();
+        log.frame(img_id, frame);
+        if (did.state_before == vo::VisualOdometry::DOING_INITIALIZATION) {
+            log.initialization(odometry->getMap(), frame, did.init, did.initialized);
+            if (did.initialized) {
+                init_frame = img_id;
+                printf("initialised at frame %d: slot %d, %d of %d matches kept, %d map points\n", img_id, did.init.slot, did.init.n_kept,
+                       (int)frame->matches_with_ref_.size(), (int)odometry->getMap()->map_points_.size());
+            } else {
+                n_rejected++;
+            }
+        } else if (did.state_before == vo::VisualOdometry::DOING_TRACKING) {
+            n_tracked += did.is_pnp_good ? 1 : 0;
+            n_lost += did.is_pnp_good ? 0 : 1;
+            n_keyframes += did.is_keyframe ? 1 : 0;
+            log.tracked(odometry->getMapOnDevice(), frame, did.is_pnp_good, did.is_keyframe);
+            if (did.is_keyframe) log.keyframe(odometry->getMap(), frame);
+        }
+        log.pose(frame);
+        cam_pose_history.push_back(frame->T_w_c_.clone());  // run_vo.cpp:139-142
+        frame->clearNoUsed();  // keeps keypoints_ and descriptors_: what the later frames match the first keyframe with
+    }
+    const string save_predicted_traj_to = basics::Config::get<string>("save_predicted_traj_to");
+    vo::writePoseToFile(save_predicted_traj_to, cam_pose_history);
+    printf("frames %d, tracked %d, lost %d, keyframes %d, map points %d -> %s\n", (int)cam_pose_history.size(), n_tracked, n_lost,
+           n_keyframes, (int)odometry->getMap()->map_points_.size(), save_predicted_traj_to.c_str());
+    if (init_frame < 0)
+        printf("never initialised: %d frames rejected, every pose is the first keyframe's\n", n_rejected);
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -96,6 +172,15 @@ int main(int argc, char** argv) {
         const vector<string> image_paths = vo::readImagePaths(dataset_dir, num_images, "/rgb_%05d.png");
         const cv::Mat K = vo::readCameraIntrinsics(dataset_name);
         const int max_num_imgs_to_proc = basics::Config::get<int>("max_num_imgs_to_proc");
+        const bool init_from_images = basics::Config::has("init_from_images") && basics::Config::get<int>("init_from_images") != 0;
+        if (init_from_images) {
+            FrameLog log;
+            if (basics::Config::has("save_frame_log_to")) {
+                log.f = fopen(basics::Config::get<string>("save_frame_log_to").c_str(), "wb");
+                if (!log.f) throw std::runtime_error("cannot open save_frame_log_to");
+            }
+            return runFromImages(image_paths, K, std::min(max_num_imgs_to_proc, (int)image_paths.size()), log);
+        }
         const vector<cv::Mat> truth = vo::readPoseFromFile(basics::Config::get<string>(sec + "true_traj_filename"));
         const int k0 = basics::Config::has("init_keyframe_0") ? basics::Config::get<int>("init_keyframe_0") : 0;
         const int k1 = basics::Config::has("init_keyframe_1") ? basics::Config::get<int>("init_keyframe_1") : 5;
@@ -146,7 +231,7 @@ int main(int argc, char** argv) {
                 n_tracked += good ? 1 : 0;
                 n_lost += good ? 0 : 1;
                 n_keyframes += is_keyframe ? 1 : 0;
-                log.tracked(st, frame, good, is_keyframe);
+                log.tracked(st.dev_map_, frame, good, is_keyframe);
                 if (is_keyframe) log.keyframe(st.map_, frame);
             }
             log.pose(frame);

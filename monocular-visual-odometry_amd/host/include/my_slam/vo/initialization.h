@@ -8,6 +8,8 @@
 //                               addKeyFrame_ on success, curr->T_w_c_ = ref->T_w_c_ otherwise
 // When the E / H rule picks a solution that does not exist (the reference would index list_R[-1]; DESIGN.md section 2,
 // deviation 12) the frame gets no inliers and the reference keyframe's pose, and isVoGoodToInit is false.
+// InitReport (optional last argument of the first and the third) keeps what mvo_init_two_view said about the frame and
+// what the branch decided, for logs (host/driver/run_vo.cpp); nothing of the branch reads it.
 #ifndef MY_SLAM_INITIALIZATION_H
 #define MY_SLAM_INITIALIZATION_H
 #include "my_slam/geometry/feature_match.h"
@@ -17,7 +19,15 @@
 namespace my_slam {
 namespace vo {
 
-inline void estimateMotionAnd3DPoints(const Frame::Ptr& curr, const Frame::Ptr& ref, const cv::Mat& K) {
+struct InitReport {
+    // mvo_init_result of the frame: the chosen solution, the length of its inlier list, the points kept, whether the depth
+    // scaling ran, the device's three criteria; good: what isVoGoodToInit returned (the decision the branch took)
+    int slot = -1, n_slot_inliers = 0, n_kept = 0, scaled = 0, criteria[3] = {0, 0, 0}, good = 0;
+    double mean_depth = 0, scale = 0, median_angle = 0, mean_pixel_dist = 0;
+};
+
+inline void estimateMotionAnd3DPoints(const Frame::Ptr& curr, const Frame::Ptr& ref, const cv::Mat& K,
+                                      InitReport* report = nullptr) {
     // -- Rename output
     vector<cv::DMatch>& inlier_matches = curr->inliers_matches_with_ref_;
     vector<cv::Point3f>& pts3d_in_curr = curr->inliers_pts3d_;
@@ -79,6 +89,17 @@ inline void estimateMotionAnd3DPoints(const Frame::Ptr& curr, const Frame::Ptr& 
     // -- compute camera pose
     curr->T_w_c_ = cv::Mat(4, 4, CV_64FC1);
     for (int i = 0; i < 16; ++i) curr->T_w_c_.at<double>(i / 4, i % 4) = res.T_w_c[i];
+    if (report) {
+        report->slot = res.slot;
+        report->n_slot_inliers = res.n_slot_inliers;
+        report->n_kept = res.n_kept;
+        report->scaled = res.scaled;
+        for (int i = 0; i < 3; ++i) report->criteria[i] = res.criteria[i];
+        report->mean_depth = res.mean_depth;
+        report->scale = res.scale;
+        report->median_angle = res.median_angle;
+        report->mean_pixel_dist = res.mean_pixel_dist;
+    }
 }
 
 inline bool isVoGoodToInit(const Frame::Ptr& curr, const Frame::Ptr& ref) {
@@ -103,15 +124,17 @@ inline bool isVoGoodToInit(const Frame::Ptr& curr, const Frame::Ptr& ref) {
 
 // vo_addFrame.cpp:36-69; st.ref_ is the first keyframe (the BLANK branch inserted it).  Returns whether the VO
 // initialised with this frame (the caller then switches to trackFrame).
-inline bool initializeWithFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat& K) {
+inline bool initializeWithFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat& K, InitReport* report = nullptr) {
     static const float max_matching_pixel_dist_in_initialization =
         basics::Config::get<float>("max_matching_pixel_dist_in_initialization");
     static const int method_index = (int)basics::Config::get<float>("feature_match_method_index_initialization");
     st.pushFrameToBuff(curr);
     geometry::matchFeatures(st.ref_->descriptors_, curr->descriptors_, curr->matches_with_ref_, method_index, false,
                             st.ref_->keypoints_, curr->keypoints_, max_matching_pixel_dist_in_initialization);
-    estimateMotionAnd3DPoints(curr, st.ref_, K);
-    if (isVoGoodToInit(curr, st.ref_)) {
+    estimateMotionAnd3DPoints(curr, st.ref_, K, report);
+    const bool good = isVoGoodToInit(curr, st.ref_);
+    if (report) report->good = good ? 1 : 0;
+    if (good) {
         pushCurrPointsToMap(st, curr);
         st.map_->insertKeyFrame(curr);  // addKeyFrame_
         st.ref_ = curr;

@@ -1,8 +1,9 @@
 // my_slam/vo/tracking_loop.h -- the DOING_TRACKING branch of VisualOdometry::addFrame (reference
 // src/vo/vo_addFrame.cpp:70-124) composed from the mirrored hot-path pieces, plus the three small members it calls
 // (checkLargeMoveForAddKeyFrame_ vo.cpp:247-266, pushCurrPointsToMap_ vo.cpp:528-576, optimizeMap_ vo.cpp:488-526).
-// It exists so that the rows can be exercised TOGETHER the way the reference chains them (tests/): the state
-// machine, initialisation and display of the reference are not part of this repository.
+// It exists so that the rows can be exercised TOGETHER the way the reference chains them (tests/); the initialisation
+// branch is my_slam/vo/initialization.h, the state machine around both my_slam/vo/vo.h.  The display of the reference
+// is not part of this repository.
 #ifndef MY_SLAM_TRACKING_LOOP_H
 #define MY_SLAM_TRACKING_LOOP_H
 #include <deque>
