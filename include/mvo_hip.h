@@ -115,6 +115,36 @@ int mvo_calc_descriptors_dev(mvo_ctx* ctx, mvo_keypoint* kps, int* n, uint8_t* d
 int mvo_select_uniform_kpts_by_grid(mvo_ctx* ctx, mvo_keypoint* kps, int* n, int image_rows,
                                     int image_cols);
 
+/* ---- undistortion -------------------------------------------------------------------------- */
+/* cv2.undistort(img, K, dist) as python_tools/undistort_all_images.py:11-37 applies it to every image of a dataset
+ * before run_vo sees it (config/config.yaml:17,39: "The images should all be undistorted"): cv::undistort with
+ * newCameraMatrix = K, i.e. initUndistortRectifyMap to 1/32 px fixed-point maps followed by remap(INTER_LINEAR,
+ * BORDER_CONSTANT, 0).  The declared arithmetic, and where it deviates from OpenCV's loops (closed form per pixel,
+ * no stripes, int32 coordinates), is DESIGN.md section 13.
+ * coeffs in OpenCV's order k1, k2, p1, p2, k3, k4, k5, k6; n_coeffs 4, 5 or 8 (entries beyond n_coeffs are ignored
+ * and taken as 0).  The 12- and 14-coefficient models (thin prism, tilt) are MVO_ERR_INVALID. */
+typedef struct {
+    double fx, fy, cx, cy;
+    double coeffs[8];
+    int32_t n_coeffs;
+} mvo_undistort_params;
+/* Builds the map of a width x height image on the device and keeps it in the ctx (python_tools/undistort_all_images.py:11-37
+ * computes it again for every image; config/config.yaml:17,39).  The same values again cost nothing; other values
+ * rebuild the map.  width at most 8192, width * height at most 2^30, fx and fy non-zero, every value finite;
+ * otherwise MVO_ERR_INVALID and the previous configuration stays. */
+int mvo_undistort_configure(mvo_ctx* ctx, const mvo_undistort_params* params, int width, int height);
+/* cv2.undistort of one image (python_tools/undistort_all_images.py:11-37; config/config.yaml:17,39).  image / out:
+ * u8, channels 1, 3 or 4, each handled independently; stride >= width * channels on both sides; out has the size
+ * and channel count of the input, bytes of out beyond width * channels of a row are not written.  MVO_ERR_STATE
+ * before mvo_undistort_configure or with another size than the configured one. */
+int mvo_undistort(mvo_ctx* ctx, const uint8_t* image, int width, int height, int stride, int channels, uint8_t* out,
+                  int out_stride);
+/* The same with source and destination in HBM (python_tools/undistort_all_images.py:11-37; config/config.yaml:17,39):
+ * what a resident pipeline places in front of mvo_calc_keypoints_dev.  d_out is the caller's and must not overlap
+ * d_image (MVO_ERR_INVALID).  Asynchronous on the ctx stream, like the extraction that follows it there. */
+int mvo_undistort_dev(mvo_ctx* ctx, const void* d_image, int width, int height, int stride, int channels,
+                      void* d_out, int out_stride);
+
 /* ---- matching ------------------------------------------------------------------------------ */
 /* cv::BFMatcher("BruteForce-Hamming")::knnMatch(k=2) as used at feature_match.cpp:203-208: exact
  * 2-NN, equal distances keep the lower train index first.  idx/dist: nq x 2 int32; a missing
@@ -492,6 +522,11 @@ int mvo_debug_get_level(mvo_ctx* ctx, int level, int blurred, uint8_t* out, int 
 /* FAST+NMS survivors of the last detection in canonical (level,row,col) order as 16-byte records
  * {int16 x, y; int32 level<<16|fast_score; float harris; float angle}. */
 int mvo_debug_get_candidates(mvo_ctx* ctx, void* out, int cap, int* n);
+/* The map of the last mvo_undistort_configure (the counterpart of initUndistortRectifyMap inside cv2.undistort,
+ * python_tools/undistort_all_images.py:11-37; config/config.yaml:17,39), row-major width x height: source column
+ * ix and row iy of the top-left tap and the 1/32 px fractions ax, ay (0..31).  Any output may be NULL.
+ * MVO_ERR_STATE without a configuration, MVO_ERR_CAPACITY when cap < width * height. */
+int mvo_debug_get_undistort_map(mvo_ctx* ctx, int32_t* ix, int32_t* iy, uint8_t* ax, uint8_t* ay, int cap);
 
 /* Record of the last mvo_solve_pnp_ransac on this ctx: models (iterations x 12: R row-major, t) and inlier
  * counts of every hypothesis, info[6] = {best iteration, iterations the sequential loop would have run,

@@ -60,6 +60,12 @@ class MvoError(RuntimeError):
         self.code = code
 
 
+class UndistortParams(C.Structure):
+    """mvo_undistort_params (include/mvo_hip.h)."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("coeffs", C.c_double * 8), ("n_coeffs", C.c_int32)]
+
+
 class InitPoses(C.Structure):
     """mvo_init_poses (include/mvo_hip.h)."""
     _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
@@ -224,6 +230,39 @@ class Context:
         n = C.c_int(len(kps))
         self._chk(self.lib.mvo_select_uniform_kpts_by_grid(self.h, _p(kps), C.byref(n), image_rows, image_cols))
         return kps[:n.value].copy()
+
+    # ---- undistortion (python_tools/undistort_all_images.py:11-37)
+    def undistort_configure(self, K, coeffs, width, height):
+        """mvo_undistort_configure: K = dict(fx, fy, cx, cy), coeffs in OpenCV's order k1, k2, p1, p2[, k3[, k4, k5, k6]]."""
+        c = np.ascontiguousarray(coeffs, np.float64).reshape(-1)
+        p = UndistortParams(float(K["fx"]), float(K["fy"]), float(K["cx"]), float(K["cy"]))
+        for i, v in enumerate(c[:8]):
+            p.coeffs[i] = v
+        p.n_coeffs = len(c)   # (a count the library does not support is the library's to reject)
+        self._chk(self.lib.mvo_undistort_configure(self.h, C.byref(p), int(width), int(height)))
+        self._undist_hw = (int(height), int(width))
+
+    def undistort(self, image):
+        """cv2.undistort(image, K, dist) with the configured K / dist -> ndarray of the same shape and dtype."""
+        img, w, h, stride, ch = _image_args(image)
+        out = np.zeros_like(img)
+        self._chk(self.lib.mvo_undistort(self.h, _p(img), w, h, stride, ch, _p(out), stride))
+        return out
+
+    def undistort_dev(self, d_in, d_out, w, h, stride, ch, out_stride):
+        """mvo_undistort_dev: device pointers; d_out is the caller's, must not overlap d_in and stays alive until the ctx
+        stream has run the call (synchronize())."""
+        self._chk(self.lib.mvo_undistort_dev(self.h, C.c_void_p(d_in), int(w), int(h), int(stride), int(ch), C.c_void_p(d_out),
+                                             int(out_stride)))
+
+    def debug_undistort_map(self):
+        """Map of the last undistort_configure -> (ix, iy int32, ax, ay uint8), each height x width."""
+        h, w = getattr(self, "_undist_hw", (0, 0))
+        n = h * w
+        ix, iy = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        ax, ay = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        self._chk(self.lib.mvo_debug_get_undistort_map(self.h, _p(ix), _p(iy), _p(ax), _p(ay), n))
+        return tuple(a[:n].reshape(h, w) for a in (ix, iy, ax, ay))
 
     # ---- matching
     def match_knn2(self, q, t):

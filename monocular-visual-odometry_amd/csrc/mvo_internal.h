@@ -160,6 +160,26 @@ struct TrackViewArgs {
 };
 struct mvo_track_state;  // device buffers of the tracking rows, allocated on first use
 
+// undistortion (undistort_kernels.hip / undistort_host.cpp)
+struct UndistortArgs {  // k_undistort_map: the model with 1 / fx, 1 / fy taken on the host, missing coefficients 0
+    double fx, fy, cx, cy, ifx, ify;
+    double k1, k2, p1, p2, k3, k4, k5, k6;
+};
+// k_undistort_map's record of one output pixel, 8 bytes: iu = cvRound(u * 32), iv = cvRound(v * 32).  The integer
+// coordinate is the arithmetic shift iu >> 5, the 1/32 px fraction iu & 31.
+struct UndistortRec {
+    int32_t iu, iv;
+};
+struct mvo_undistort_state {  // owned by undistort_host.cpp, released through mvo_ctx::undist_release
+    bool configured = false;
+    mvo_undistort_params params{};  // as configured, coefficients beyond n_coeffs zeroed
+    int w = 0, h = 0;
+    UndistortRec* d_map = nullptr;
+    size_t map_cap = 0;  // records
+    uint8_t *d_src = nullptr, *d_dst = nullptr;  // staging of the host-pointer form
+    size_t src_cap = 0, dst_cap = 0;
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -233,6 +253,10 @@ struct mvo_ctx {
     bool init_called = false;
     std::vector<float> init_p_curr;
     std::vector<double> init_cosang, init_pixdist;
+    // --- undistortion: allocated by the first mvo_undistort_configure.  mvo_destroy releases it through the pointer, so
+    // that mvo_api.cpp carries no reference into undistort_host.cpp (a build without that file still links)
+    mvo_undistort_state* undist = nullptr;
+    void (*undist_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -317,6 +341,10 @@ int track_launch_init_triangulate(mvo_ctx* ctx, const float* d_kp1, const float*
 int track_launch_init_finish(mvo_ctx* ctx, const float* d_pts, const int32_t* d_list, int m, const double* d_R,
                              const double* d_t, const float* d_kp1, const float* d_kp2, const double* T_w_c_curr,
                              const double* T_w_c_ref, float* d_p_curr, double* d_cosang, double* d_pixdist);
+// undistort_kernels.hip
+int undistort_launch_map(mvo_ctx* ctx, const UndistortArgs& a, int w, int h, UndistortRec* d_map);
+int undistort_launch_remap(mvo_ctx* ctx, const UndistortRec* d_map, const uint8_t* d_src, int w, int h, int stride,
+                           int channels, uint8_t* d_out, int out_stride);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

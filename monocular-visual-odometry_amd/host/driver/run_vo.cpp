@@ -18,6 +18,10 @@
 //      (`true_traj_filename`, config.yaml:24; keys `init_keyframe_0/1` pick the frames, default 0 and 5): their matches
 //      are filtered and triangulated exactly as a keyframe insertion does it (vo_addFrame.cpp:96-118), which also fixes
 //      the scale.  From then on nothing of the ground truth is used.
+// Optional keys `camera_info.k1`, `.k2`, `.p1`, `.p2`, `.k3` in the dataset section (cv2.calibrateCamera's vector; a missing
+// one is 0): with at least one of them every image is undistorted on the device right after basics::imread
+// (my_slam/basics/undistort.h = cv2.undistort(img, K, dist) of python_tools/undistort_all_images.py:11-37), so the frame holds
+// what an undistorted file on disk would have held.  Without them the images are taken as undistorted (config.yaml:17,39).
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -29,6 +33,7 @@
 #include <cstring>
 
 #include "my_slam/basics/image_io.h"
+#include "my_slam/basics/undistort.h"
 #include "my_slam/vo/tracking_loop.h"
 #include "my_slam/vo/vo.h"
 #include "my_slam/vo/vo_io.h"
@@ -36,6 +41,9 @@
 // Bound weakly: a build of the library without the host side of the initialisation (the emulated libmvo_sim.so of tests/sim)
 // still serves the seeded start; asking such a library for `init_from_images` is an error, not a fall-back.
 #pragma weak mvo_init_two_view
+// ... or without the undistortion: asking such a library for it (`camera_info.k1` ...) is an error as well
+#pragma weak mvo_undistort_configure
+#pragma weak mvo_undistort
 
 using namespace my_slam;
 
@@ -112,14 +120,21 @@ struct FrameLog {
     }
 };
 
+// basics::imread, then basics::undistort when the dataset section carries distortion coefficients
+cv::Mat readFrameImage(const string& path, const cv::Mat& K, const vector<double>& dist) {
+    cv::Mat img = basics::imread(path);
+    if (img.data == nullptr || dist.empty()) return img;
+    return basics::undistort(img, K, dist);
+}
+
 // `init_from_images: 1`: the reference's loop (run_vo.cpp:110-148) around VisualOdometry::addFrame
-int runFromImages(const vector<string>& image_paths, const cv::Mat& K, int n_proc, FrameLog& log) {
+int runFromImages(const vector<string>& image_paths, const cv::Mat& K, const vector<double>& dist, int n_proc, FrameLog& log) {
     if (!mvo_init_two_view) throw std::runtime_error("init_from_images: this libmvo_hip.so has no mvo_init_two_view");
     vo::VisualOdometry::Ptr odometry(new vo::VisualOdometry(K));
     vector<cv::Mat> cam_pose_history;
     int n_tracked = 0, n_lost = 0, n_keyframes = 0, n_rejected = 0, init_frame = -1;
     for (int img_id = 0; img_id < n_proc; img_id++) {
-        cv::Mat rgb_img = basics::imread(image_paths[img_id]);
+        cv::Mat rgb_img = readFrameImage(image_paths[img_id], K, dist);
         if (rgb_img.data == nullptr) {
             printf("The image file %s is empty. Finished.\n", image_paths[img_id].c_str());
             break;
@@ -171,6 +186,12 @@ int main(int argc, char** argv) {
         const int num_images = basics::Config::get<int>(sec + "num_images");
         const vector<string> image_paths = vo::readImagePaths(dataset_dir, num_images, "/rgb_%05d.png");
         const cv::Mat K = vo::readCameraIntrinsics(dataset_name);
+        const vector<double> dist = vo::readCameraDistortion(dataset_name);
+        if (!dist.empty()) {
+            if (!mvo_undistort_configure || !mvo_undistort)
+                throw std::runtime_error("camera_info.k1 ... k3: this libmvo_hip.so has no mvo_undistort");
+            printf("undistorting every image: k1 %g, k2 %g, p1 %g, p2 %g, k3 %g\n", dist[0], dist[1], dist[2], dist[3], dist[4]);
+        }
         const int max_num_imgs_to_proc = basics::Config::get<int>("max_num_imgs_to_proc");
         const bool init_from_images = basics::Config::has("init_from_images") && basics::Config::get<int>("init_from_images") != 0;
         if (init_from_images) {
@@ -179,7 +200,7 @@ int main(int argc, char** argv) {
                 log.f = fopen(basics::Config::get<string>("save_frame_log_to").c_str(), "wb");
                 if (!log.f) throw std::runtime_error("cannot open save_frame_log_to");
             }
-            return runFromImages(image_paths, K, std::min(max_num_imgs_to_proc, (int)image_paths.size()), log);
+            return runFromImages(image_paths, K, dist, std::min(max_num_imgs_to_proc, (int)image_paths.size()), log);
         }
         const vector<cv::Mat> truth = vo::readPoseFromFile(basics::Config::get<string>(sec + "true_traj_filename"));
         const int k0 = basics::Config::has("init_keyframe_0") ? basics::Config::get<int>("init_keyframe_0") : 0;
@@ -196,7 +217,7 @@ int main(int argc, char** argv) {
         int n_tracked = 0, n_lost = 0, n_keyframes = 0;
         const int n_proc = std::min(max_num_imgs_to_proc, (int)image_paths.size());
         for (int img_id = 0; img_id < n_proc; img_id++) {
-            cv::Mat rgb_img = basics::imread(image_paths[img_id]);
+            cv::Mat rgb_img = readFrameImage(image_paths[img_id], K, dist);
             if (rgb_img.data == nullptr) {
                 printf("The image file %s is empty. Finished.\n", image_paths[img_id].c_str());
                 break;

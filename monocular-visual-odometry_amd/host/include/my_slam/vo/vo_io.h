@@ -39,6 +39,24 @@ inline cv::Mat readCameraIntrinsics(const string& dataset_section) {
     return K;
 }
 
+// The distortion coefficients of the selected dataset section, in the order of cv2.calibrateCamera's vector: the optional
+// keys camera_info.k1, .k2, .p1, .p2, .k3 (a missing one is 0).  Empty when the section has none of them: the images
+// are undistorted already, as the reference's config.yaml:17,39 asks (python_tools/undistort_all_images.py:11-37).
+inline vector<double> readCameraDistortion(const string& dataset_section) {
+    const string p = dataset_section.empty() ? "" : dataset_section + ".";
+    static const char* const names[5] = {"k1", "k2", "p1", "p2", "k3"};
+    vector<double> dist(5, 0.0);
+    bool any = false;
+    for (int i = 0; i < 5; i++) {
+        const string key = p + "camera_info." + names[i];
+        if (!basics::Config::has(key)) continue;
+        dist[i] = basics::Config::get<double>(key);
+        any = true;
+    }
+    if (!any) dist.clear();
+    return dist;
+}
+
 // vo_io.cpp:51-78
 inline void writePoseToFile(const string filename, const vector<cv::Mat>& list_T) {
     std::ofstream fout(filename);
