@@ -174,6 +174,43 @@ int mvo_match_features_dev(mvo_ctx* ctx, const void* d_d1, int n1, const void* d
 /* geometry::removeDuplicatedMatches (feature_match.cpp:241-260), host-side, in place. */
 int mvo_remove_duplicated_matches(mvo_dmatch* m, int* n);
 
+/* ---- pose-guided matching ------------------------------------------------------------------- */
+/* What the reference names as its missing piece and has no function for: README.md:212 (Results: "too few keypoints
+ * matches ... doing guided matching based on the estimated camera motion") and README.md:272 (To Do: "Utilize epipolar
+ * constraint to do feature matching").  Frame 1 is the query, frame 2 the train; F is 3 x 3 f64 row-major with
+ * x2^T F x1 = 0 in pixels.  A pair (i, j) competes only if train keypoint j lies within its tolerance of the epipolar
+ * line of query i; the arithmetic of line and gate is declared operation by operation in DESIGN.md section 14:
+ *   a = (F0 x + F1 y) + F2, b = (F3 x + F4 y) + F5, c = (F6 x + F7 y) + F8, nrm = a a + b b       (x, y = qxy[i] as f64)
+ *   num = (a u + b v) + c;  pass = nrm > 0 && num num <= tol2[j] nrm                                (u, v = txy[j] as f64)
+ *   tol2[j] = tl tl, tl = max_line_px * (t_scale ? t_scale[j] : 1)
+ * The gate is inclusive; a NaN or a line with nrm == 0 gives the query no candidates.
+ * MVO_ERR_INVALID: a null pointer with a positive count, a non-finite F entry, max_line_px negative or NaN, a t_scale
+ * entry negative or not finite.  MVO_ERR_CAPACITY: nt > 65535.  nq == 0 or nt == 0 succeed (nt == 0: every idx -1). */
+/* README.md:212, README.md:272.  Raw: per query the two nearest gated trains in 256-bit Hamming space, equal distances
+ * keep the lower train index first (the tie rule of mvo_match_knn2); a missing neighbour is (-1, INT32_MAX).
+ * idx / dist: nq x 2 int32; n_candidates (optional, nq): the number of trains that passed the gate. */
+int mvo_match_knn2_epipolar(mvo_ctx* ctx, const uint8_t* q, const float* qxy, int nq, const uint8_t* t,
+                            const float* txy, const float* t_scale /* nt or NULL */, int nt, const double* F,
+                            double max_line_px, int32_t* idx, int32_t* dist, int32_t* n_candidates);
+/* README.md:212, README.md:272.  The same with both descriptor sets already in HBM (the pointers
+ * mvo_calc_descriptors_dev returns); qxy, txy and t_scale stay host pointers. */
+int mvo_match_knn2_epipolar_dev(mvo_ctx* ctx, const void* d_q, const float* qxy, int nq, const void* d_t,
+                                const float* txy, const float* t_scale, int nt, const double* F, double max_line_px,
+                                int32_t* idx, int32_t* dist, int32_t* n_candidates);
+/* README.md:212, README.md:272.  The raw call followed by the filter: query i is kept if idx0 >= 0, d0 <= max_hamming
+ * and (idx1 < 0 or (double)d0 < lowe_ratio * (double)d1) -- a single candidate passes on the ceiling alone.  Then one
+ * query per train survives: the smallest distance, on equal distance the lower queryIdx (independent of order, unlike
+ * removeDuplicatedMatches).  out is sorted by trainIdx; imgIdx 0 and distance = (float)d0 as mvo_match_features fills
+ * them.  MVO_ERR_CAPACITY (with *n set) if cap is too small. */
+int mvo_match_features_epipolar(mvo_ctx* ctx, const uint8_t* d1, const float* xy1, int n1, const uint8_t* d2,
+                                const float* xy2, const float* scale2, int n2, const double* F, double max_line_px,
+                                double lowe_ratio, int max_hamming, mvo_dmatch* out, int cap, int* n);
+/* README.md:212 ("based on the estimated camera motion").  Host-side, no ctx: F with x2^T F x1 = 0 from the two
+ * camera-to-world poses (row-major 4 x 4) and the intrinsics: T_2_1 = inv(T_w_c_2) * T_w_c_1 (mvo_invert_pose),
+ * E = [t]x R, F = K^-T E K^-1.  MVO_ERR_INVALID if a pose is singular or fx / fy is 0. */
+int mvo_fundamental_from_poses(const double* T_w_c_1, const double* T_w_c_2, double fx, double fy, double cx,
+                               double cy, double* F);
+
 /* ---- bundle adjustment --------------------------------------------------------------------- */
 /* The graph optimization::bundleAdjustment builds (src/optimization/g2o_ba.cpp:172-317), flattened:
  * pose vertices 0..F-1 (VertexSE3Expmap), point vertices (VertexSBAPointXYZ, marginalized), one

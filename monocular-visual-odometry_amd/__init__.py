@@ -316,6 +316,56 @@ class Context:
                                                   len(out), C.byref(n)))
         return out[:n.value].copy()
 
+    # ---- pose-guided matching (README.md:212, README.md:272 of the reference: named there, not implemented)
+    @staticmethod
+    def _epipolar_args(qxy, txy, t_scale, F):
+        qxy = np.ascontiguousarray(qxy, np.float32).reshape(-1, 2)
+        txy = np.ascontiguousarray(txy, np.float32).reshape(-1, 2)
+        if t_scale is not None:
+            t_scale = np.ascontiguousarray(t_scale, np.float32).reshape(-1)
+            if len(t_scale) != len(txy):
+                raise ValueError("t_scale needs one entry per train keypoint")
+        return qxy, txy, t_scale, np.ascontiguousarray(F, np.float64).reshape(9)
+
+    def match_knn2_epipolar(self, q, qxy, t, txy, F, max_line_px, t_scale=None):
+        """mvo_match_knn2_epipolar: the two nearest trains within t_scale[j] * max_line_px of each query's epipolar line
+        (x2^T F x1 = 0, query = frame 1) -> (idx nq x 2, dist nq x 2, n_candidates nq)."""
+        q = np.ascontiguousarray(q, np.uint8).reshape(-1, 32)
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        qxy, txy, t_scale, F = self._epipolar_args(qxy, txy, t_scale, F)
+        if len(qxy) != len(q) or len(txy) != len(t):
+            raise ValueError("one keypoint position per descriptor")
+        idx, dist = np.zeros((len(q), 2), np.int32), np.zeros((len(q), 2), np.int32)
+        cnt = np.zeros(len(q), np.int32)
+        self._chk(self.lib.mvo_match_knn2_epipolar(self.h, _p(q), _p(qxy), len(q), _p(t), _p(txy), _p(t_scale), len(t), _p(F),
+                                                   C.c_double(max_line_px), _p(idx), _p(dist), _p(cnt)))
+        return idx, dist, cnt
+
+    def match_knn2_epipolar_dev(self, d_q, qxy, d_t, txy, F, max_line_px, t_scale=None):
+        """The same with the descriptors in HBM (device pointers); the counts come from qxy / txy."""
+        qxy, txy, t_scale, F = self._epipolar_args(qxy, txy, t_scale, F)
+        nq, nt = len(qxy), len(txy)
+        idx, dist, cnt = np.zeros((nq, 2), np.int32), np.zeros((nq, 2), np.int32), np.zeros(nq, np.int32)
+        self._chk(self.lib.mvo_match_knn2_epipolar_dev(self.h, C.c_void_p(d_q), _p(qxy), nq, C.c_void_p(d_t), _p(txy), _p(t_scale),
+                                                       nt, _p(F), C.c_double(max_line_px), _p(idx), _p(dist), _p(cnt)))
+        return idx, dist, cnt
+
+    def match_features_epipolar(self, d1, xy1, d2, xy2, F, max_line_px, lowe_ratio, max_hamming, scale2=None, cap=None):
+        """mvo_match_features_epipolar: the raw call, the ceiling / ratio filter, one query per train -> DMATCH_DTYPE
+        sorted by trainIdx."""
+        d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 32)
+        d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 32)
+        xy1, xy2, scale2, F = self._epipolar_args(xy1, xy2, scale2, F)
+        if len(xy1) != len(d1) or len(xy2) != len(d2):
+            raise ValueError("one keypoint position per descriptor")
+        cap = min(len(d1), len(d2)) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        n = C.c_int()
+        self._chk(self.lib.mvo_match_features_epipolar(self.h, _p(d1), _p(xy1), len(d1), _p(d2), _p(xy2), _p(scale2), len(d2),
+                                                       _p(F), C.c_double(max_line_px), C.c_double(lowe_ratio), int(max_hamming),
+                                                       _p(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
     # ---- bundle adjustment
     def _ba_problem(self, poses, points, edge_pose, edge_point, edge_uv, focal, cx, cy, info, huber_delta,
                     fix_points, pose_fixed, max_iterations):
@@ -778,6 +828,24 @@ def rodrigues(rvec):
     if load_library().mvo_rodrigues(_p(r), _p(R)) != MVO_OK:
         raise MvoError(MVO_ERR_INVALID, "mvo_rodrigues")
     return R
+
+
+def fundamental_from_poses(T_w_c_1, T_w_c_2, K):
+    """mvo_fundamental_from_poses: F (3 x 3, x2^T F x1 = 0 in pixels) of two camera-to-world poses; K = 3 x 3 or
+    dict(fx, fy, cx, cy).  Host-side, needs no GPU."""
+    T1 = np.ascontiguousarray(T_w_c_1, np.float64).reshape(16)
+    T2 = np.ascontiguousarray(T_w_c_2, np.float64).reshape(16)
+    if isinstance(K, dict):
+        fx, fy, cx, cy = K["fx"], K["fy"], K["cx"], K["cy"]
+    else:
+        K = np.asarray(K, np.float64)
+        fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    F = np.zeros(9)
+    r = load_library().mvo_fundamental_from_poses(_p(T1), _p(T2), C.c_double(fx), C.c_double(fy), C.c_double(cx),
+                                                  C.c_double(cy), _p(F))
+    if r != MVO_OK:
+        raise MvoError(r, "mvo_fundamental_from_poses: singular pose or fx / fy 0")
+    return F.reshape(3, 3)
 
 
 def retain_good_triangulation(pts3d_in_curr, T_w_c_curr, T_w_c_ref, min_triang_angle=1.0, max_ratio_to_median=20.0):

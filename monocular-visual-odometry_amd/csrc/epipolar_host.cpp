@@ -1,0 +1,223 @@
+// csrc/epipolar_host.cpp -- host side of the pose-guided matcher (include/mvo_hip.h: mvo_match_knn2_epipolar,
+// mvo_match_knn2_epipolar_dev, mvo_match_features_epipolar, mvo_fundamental_from_poses): argument checks, the per-train
+// tolerance, staging, the filter and the one-query-per-train rule.  The kernel is in epipolar_kernels.hip, the arithmetic in
+// DESIGN.md section 14.  No other translation unit refers to this one: mvo_destroy reaches epipolar_release through
+// mvo_ctx::epi_release.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mvo_internal.h"
+
+namespace {
+
+const int kMaxTrains = 65535;  // the train index lives in the low 16 bits of a key
+
+void epipolar_release(mvo_ctx* ctx) {
+    mvo_epipolar_state* e = ctx->epi;
+    if (!e) return;
+    void* dev[] = {e->d_q, e->d_qxy, e->d_part, e->d_out, e->d_t, e->d_txy, e->d_tol2};
+    for (void* p : dev)
+        if (p) mvo_free_on_current_device(p);
+    delete e;
+    ctx->epi = nullptr;
+}
+
+int ensure_bufs(mvo_ctx* ctx, int nq, int nt) {
+    if (!ctx->epi) {
+        ctx->epi = new mvo_epipolar_state();
+        ctx->epi_release = epipolar_release;
+    }
+    mvo_epipolar_state* e = ctx->epi;
+    if (nq > e->cap_q) {
+        void* old[] = {e->d_q, e->d_qxy, e->d_part, e->d_out};
+        for (void* p : old)
+            if (p) mvo_free_on_current_device(p);
+        e->d_q = nullptr, e->d_qxy = nullptr, e->d_part = nullptr, e->d_out = nullptr;
+        e->cap_q = 0;
+        const size_t cap = (size_t)std::max(4096, nq + nq / 2);
+        MVO_HIP(hipMalloc((void**)&e->d_q, cap * 32));
+        MVO_HIP(hipMalloc((void**)&e->d_qxy, cap * 8));
+        MVO_HIP(hipMalloc((void**)&e->d_out, cap * 20));
+        // partial key pairs, partial counts, one arrival counter per group of 64 queries (self re-arming, zeroed once)
+        const size_t keys = EK_MAX_GROUPS * cap * 8, cnts = EK_MAX_GROUPS * cap * 4, ctr = (cap / 64 + 2) * 4;
+        MVO_HIP(hipMalloc((void**)&e->d_part, keys + cnts + ctr));
+        e->d_part_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys);
+        e->d_arrive = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys + cnts);
+        MVO_HIP(hipMemsetAsync(e->d_arrive, 0, ctr, ctx->stream));
+        e->cap_q = (int)cap;
+    }
+    if (nt > e->cap_t) {
+        void* old[] = {e->d_t, e->d_txy, e->d_tol2};
+        for (void* p : old)
+            if (p) mvo_free_on_current_device(p);
+        e->d_t = nullptr, e->d_txy = nullptr, e->d_tol2 = nullptr;
+        e->cap_t = 0;
+        const size_t cap = (size_t)std::max(4096, nt + nt / 2);
+        MVO_HIP(hipMalloc((void**)&e->d_t, cap * 32));
+        MVO_HIP(hipMalloc((void**)&e->d_txy, cap * 8));
+        MVO_HIP(hipMalloc((void**)&e->d_tol2, cap * 8));
+        e->cap_t = (int)cap;
+    }
+    return MVO_OK;
+}
+
+// the checks every form shares; MVO_OK with *done set: nothing to launch, the outputs are filled
+int check_and_trivial(mvo_ctx* ctx, const void* q, const float* qxy, int nq, const void* t, const float* txy, const float* t_scale,
+                      int nt, const double* F, double max_line_px, int32_t* idx, int32_t* dist, int32_t* n_candidates, bool* done) {
+    *done = false;
+    if (!ctx) return MVO_ERR_INVALID;
+    if (nq < 0 || nt < 0 || !F || (nq && (!q || !qxy || !idx || !dist)) || (nt && (!t || !txy)))
+        return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: bad arguments", hipSuccess);
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(F[k])) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: F is not finite", hipSuccess);
+    if (!(max_line_px >= 0)) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: max_line_px negative or NaN", hipSuccess);
+    if (nt > kMaxTrains) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_match_knn2_epipolar: more than 65535 train descriptors", hipSuccess);
+    if (t_scale)
+        for (int j = 0; j < nt; ++j)
+            if (!std::isfinite(t_scale[j]) || t_scale[j] < 0)
+                return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: t_scale entry negative or not finite", hipSuccess);
+    if (nq == 0 || nt == 0) {
+        for (int i = 0; i < nq; ++i) {
+            idx[2 * i] = idx[2 * i + 1] = -1;
+            dist[2 * i] = dist[2 * i + 1] = INT_MAX;
+            if (n_candidates) n_candidates[i] = 0;
+        }
+        *done = true;
+    }
+    return MVO_OK;
+}
+
+// d_q / d_t: device descriptors; qxy, txy, t_scale: host.  nq, nt >= 1, arguments checked.
+int run(mvo_ctx* ctx, const uint8_t* d_q, const float* qxy, int nq, const uint8_t* d_t, const float* txy, const float* t_scale,
+        int nt, const double* F, double max_line_px, int32_t* idx, int32_t* dist, int32_t* n_candidates) {
+    mvo_epipolar_state* e = ctx->epi;
+    std::vector<double> tol2(nt);
+    for (int j = 0; j < nt; ++j) {
+        const double tl = max_line_px * (t_scale ? (double)t_scale[j] : 1.0);
+        tol2[j] = tl * tl;
+    }
+    EpipolarArgs a;
+    std::memcpy(a.f, F, sizeof a.f);
+    // the kernel writes the nq x (idx[2], dist[2]) block and the counts straight into the pinned staging buffer
+    int r = mvo_ensure_pinned(ctx, (size_t)nq * 20);
+    if (r) return r;
+    MVO_HIP(hipMemcpyAsync(e->d_qxy, qxy, (size_t)nq * 8, hipMemcpyHostToDevice, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(e->d_txy, txy, (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(e->d_tol2, tol2.data(), (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
+    ExtractGate gate(ctx);
+    if ((r = epipolar_launch_knn2(ctx, d_q, e->d_qxy, nq, d_t, e->d_txy, e->d_tol2, nt, a, e->d_part, e->d_part_cnt, e->d_arrive,
+                                  reinterpret_cast<int32_t*>(ctx->h_pin))))
+        return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (tol2 is pageable: its copy has left the vector by now either way)
+    gate.release();
+    if (ctx->prof) mvo_prof_collect(ctx);
+    std::memcpy(idx, ctx->h_pin, (size_t)nq * 8);
+    std::memcpy(dist, ctx->h_pin + (size_t)nq * 8, (size_t)nq * 8);
+    if (n_candidates) std::memcpy(n_candidates, ctx->h_pin + (size_t)nq * 16, (size_t)nq * 4);
+    return MVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// README.md:212 ("doing guided matching based on the estimated camera motion"), README.md:272 ("Utilize epipolar constraint
+// to do feature matching"): the reference names the method and has no function for it
+int mvo_match_knn2_epipolar(mvo_ctx* ctx, const uint8_t* q, const float* qxy, int nq, const uint8_t* t, const float* txy,
+                            const float* t_scale, int nt, const double* F, double max_line_px, int32_t* idx, int32_t* dist,
+                            int32_t* n_candidates) {
+    bool done;
+    int r = check_and_trivial(ctx, q, qxy, nq, t, txy, t_scale, nt, F, max_line_px, idx, dist, n_candidates, &done);
+    if (r || done) return r;
+    MVO_HIP(hipSetDevice(ctx->device));
+    if ((r = ensure_bufs(ctx, nq, nt))) return r;
+    mvo_epipolar_state* e = ctx->epi;
+    MVO_HIP(hipMemcpyAsync(e->d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
+    MVO_HIP(hipMemcpyAsync(e->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
+    return run(ctx, e->d_q, qxy, nq, e->d_t, txy, t_scale, nt, F, max_line_px, idx, dist, n_candidates);
+}
+
+// README.md:212, README.md:272: the same with both descriptor sets already in HBM
+int mvo_match_knn2_epipolar_dev(mvo_ctx* ctx, const void* d_q, const float* qxy, int nq, const void* d_t, const float* txy,
+                                const float* t_scale, int nt, const double* F, double max_line_px, int32_t* idx, int32_t* dist,
+                                int32_t* n_candidates) {
+    bool done;
+    int r = check_and_trivial(ctx, d_q, qxy, nq, d_t, txy, t_scale, nt, F, max_line_px, idx, dist, n_candidates, &done);
+    if (r || done) return r;
+    MVO_HIP(hipSetDevice(ctx->device));
+    if ((r = ensure_bufs(ctx, nq, nt))) return r;
+    return run(ctx, (const uint8_t*)d_q, qxy, nq, (const uint8_t*)d_t, txy, t_scale, nt, F, max_line_px, idx, dist, n_candidates);
+}
+
+// README.md:212, README.md:272: the raw call, the filter, one query per train
+int mvo_match_features_epipolar(mvo_ctx* ctx, const uint8_t* d1, const float* xy1, int n1, const uint8_t* d2, const float* xy2,
+                                const float* scale2, int n2, const double* F, double max_line_px, double lowe_ratio, int max_hamming,
+                                mvo_dmatch* out, int cap, int* n) {
+    if (!ctx) return MVO_ERR_INVALID;
+    if (!n || n1 < 0 || n2 < 0) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_features_epipolar: bad arguments", hipSuccess);
+    *n = 0;
+    std::vector<int32_t> idx(2 * (size_t)n1 + 2), dist(2 * (size_t)n1 + 2);
+    int r = mvo_match_knn2_epipolar(ctx, d1, xy1, n1, d2, xy2, scale2, n2, F, max_line_px, idx.data(), dist.data(), nullptr);
+    if (r) return r;
+    // per train the claiming query with the smallest (distance, queryIdx); queries arrive in ascending order
+    std::vector<int32_t> owner(n2 > 0 ? n2 : 1, -1);
+    for (int i = 0; i < n1; ++i) {
+        const int j = idx[2 * i], d0 = dist[2 * i];
+        if (j < 0 || d0 > max_hamming) continue;
+        if (idx[2 * i + 1] >= 0 && !((double)d0 < lowe_ratio * (double)dist[2 * i + 1])) continue;
+        if (owner[j] < 0 || d0 < dist[2 * owner[j]]) owner[j] = i;
+    }
+    int cnt = 0;
+    for (int j = 0; j < n2; ++j) cnt += owner[j] >= 0 ? 1 : 0;
+    *n = cnt;
+    if (cnt > cap || (cnt && !out)) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "match buffer too small", hipSuccess);
+    int k = 0;
+    for (int j = 0; j < n2; ++j)
+        if (owner[j] >= 0) out[k++] = {owner[j], j, 0, (float)dist[2 * owner[j]]};
+    return MVO_OK;
+}
+
+// README.md:212 ("based on the estimated camera motion"): the fundamental matrix of the two estimated poses
+int mvo_fundamental_from_poses(const double* T_w_c_1, const double* T_w_c_2, double fx, double fy, double cx, double cy, double* F) {
+    if (!T_w_c_1 || !T_w_c_2 || !F || fx == 0 || fy == 0 || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) ||
+        !std::isfinite(cy))
+        return MVO_ERR_INVALID;
+    double Ti1[16], Ti2[16], T[16];
+    if (mvo_invert_pose(T_w_c_1, Ti1) != MVO_OK || mvo_invert_pose(T_w_c_2, Ti2) != MVO_OK) return MVO_ERR_INVALID;
+    for (int i = 0; i < 4; ++i)  // T_2_1 = inv(T_w_c_2) * T_w_c_1, summed k = 0..3 in order
+        for (int j = 0; j < 4; ++j) {
+            double s = 0;
+            for (int k = 0; k < 4; ++k) s += Ti2[4 * i + k] * T_w_c_1[4 * k + j];
+            T[4 * i + j] = s;
+        }
+    const double tx = T[3], ty = T[7], tz = T[11];
+    const double S[9] = {0, -tz, ty, tz, 0, -tx, -ty, tx, 0};  // [t]x
+    const double Ki[9] = {1 / fx, 0, -cx / fx, 0, 1 / fy, -cy / fy, 0, 0, 1};
+    double E[9], M[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double s = 0;
+            for (int k = 0; k < 3; ++k) s += S[3 * i + k] * T[4 * k + j];
+            E[3 * i + j] = s;
+        }
+    for (int i = 0; i < 3; ++i)  // M = E K^-1
+        for (int j = 0; j < 3; ++j) {
+            double s = 0;
+            for (int k = 0; k < 3; ++k) s += E[3 * i + k] * Ki[3 * k + j];
+            M[3 * i + j] = s;
+        }
+    for (int i = 0; i < 3; ++i)  // F = K^-T M
+        for (int j = 0; j < 3; ++j) {
+            double s = 0;
+            for (int k = 0; k < 3; ++k) s += Ki[3 * k + i] * M[3 * k + j];
+            F[3 * i + j] = s;
+        }
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(F[k])) return MVO_ERR_INVALID;
+    return MVO_OK;
+}
+
+}  // extern "C"

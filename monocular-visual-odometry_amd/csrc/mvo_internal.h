@@ -180,6 +180,21 @@ struct mvo_undistort_state {  // owned by undistort_host.cpp, released through m
     size_t src_cap = 0, dst_cap = 0;
 };
 
+// pose-guided matching (epipolar_kernels.hip / epipolar_host.cpp)
+struct EpipolarArgs {  // k_knn2_epipolar: F row-major, x2^T F x1 = 0
+    double f[9];
+};
+#define EK_MAX_GROUPS 8  // train groups of k_knn2_epipolar (workgroups per group of 64 queries)
+struct mvo_epipolar_state {  // owned by epipolar_host.cpp, released through mvo_ctx::epi_release
+    uint8_t *d_q = nullptr, *d_t = nullptr;  // staging of the host-pointer form
+    float *d_qxy = nullptr, *d_txy = nullptr;
+    double* d_tol2 = nullptr;
+    unsigned long long* d_part = nullptr;  // EK_MAX_GROUPS x cap_q partial key pairs, then as many counts, then the arrival counters
+    int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
+    int32_t* d_out = nullptr;  // cap_q x 5: where a caller that keeps the result on the device has it delivered
+    int cap_q = 0, cap_t = 0;
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -257,6 +272,9 @@ struct mvo_ctx {
     // that mvo_api.cpp carries no reference into undistort_host.cpp (a build without that file still links)
     mvo_undistort_state* undist = nullptr;
     void (*undist_release)(mvo_ctx*) = nullptr;
+    // --- pose-guided matching: allocated by the first mvo_match_knn2_epipolar*, released like the undistortion
+    mvo_epipolar_state* epi = nullptr;
+    void (*epi_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -345,6 +363,11 @@ int track_launch_init_finish(mvo_ctx* ctx, const float* d_pts, const int32_t* d_
 int undistort_launch_map(mvo_ctx* ctx, const UndistortArgs& a, int w, int h, UndistortRec* d_map);
 int undistort_launch_remap(mvo_ctx* ctx, const UndistortRec* d_map, const uint8_t* d_src, int w, int h, int stride,
                            int channels, uint8_t* d_out, int out_stride);
+// epipolar_kernels.hip
+int epipolar_groups(int nt);
+int epipolar_launch_knn2(mvo_ctx* ctx, const uint8_t* d_q, const float* d_qxy, int nq, const uint8_t* d_t, const float* d_txy,
+                         const double* d_tol2, int nt, const EpipolarArgs& a, unsigned long long* d_part, int32_t* d_part_cnt,
+                         int32_t* d_arrive, int32_t* out);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -22,6 +22,15 @@
 // one is 0): with at least one of them every image is undistorted on the device right after basics::imread
 // (my_slam/basics/undistort.h = cv2.undistort(img, K, dist) of python_tools/undistort_all_images.py:11-37), so the frame holds
 // what an undistorted file on disk would have held.  Without them the images are taken as undistorted (config.yaml:17,39).
+// Optional key `triangulation_match_by_epipolar_line` (0 / 1, default 0): 1 makes every keyframe insertion while tracking (and
+// the seeding of the map under `init_from_images: 0`) match the new keyframe with its reference keyframe along the epipolar
+// lines of their two estimated poses (my_slam/geometry/epipolar_match.h; the reference's README.md:212,272) instead of over all
+// pairs (vo_addFrame.cpp:99).  The initialisation has no pose yet and keeps matchFeatures.  Its three parameters, optional as
+// well: `epipolar_match_max_line_dist` (px at pyramid level 0, default 2.0), `epipolar_match_lowe_ratio` (default 0.8),
+// `epipolar_match_max_hamming` (default 64).  With the key on, a keyframe's part of the frame log carries two more records
+// after MREF: EPIF = int32 id_ of the reference keyframe, int32 0, the 9 f64 of F (x_curr^T F x_ref = 0), row-major; and
+// EPIR = the 16 f64 of the reference keyframe's T_w_c_ as F was computed from it (its POSE record dates from its own frame;
+// the window bundle adjustment of the frames since has moved it).  F = mvo_fundamental_from_poses(EPIR, this frame's POSE).
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -44,6 +53,9 @@
 // ... or without the undistortion: asking such a library for it (`camera_info.k1` ...) is an error as well
 #pragma weak mvo_undistort_configure
 #pragma weak mvo_undistort
+// ... or without the pose-guided matcher (`triangulation_match_by_epipolar_line`): an error, not a fall-back
+#pragma weak mvo_fundamental_from_poses
+#pragma weak mvo_match_features_epipolar
 
 using namespace my_slam;
 
@@ -82,6 +94,16 @@ struct FrameLog {
     }
     void keyframe(const vo::Map::Ptr& map, const vo::Frame::Ptr& fr) {
         vec("MREF", fr->matches_with_ref_);
+        if (!fr->epipolar_F_.empty()) {  // `triangulation_match_by_epipolar_line: 1`
+            unsigned char rec[8 + 72];
+            const int head[2] = {fr->epipolar_ref_id_, 0};
+            std::memcpy(rec, head, 8);
+            std::memcpy(rec + 8, fr->epipolar_F_.ptr<double>(0), 72);
+            put("EPIF", rec, sizeof rec);
+            double T[16];
+            for (int i = 0; i < 16; ++i) T[i] = fr->epipolar_ref_T_w_c_.at<double>(i / 4, i % 4);
+            put("EPIR", T, sizeof T);
+        }
         triangulated(fr);
         mapAfter(map);
     }
@@ -191,6 +213,11 @@ int main(int argc, char** argv) {
             if (!mvo_undistort_configure || !mvo_undistort)
                 throw std::runtime_error("camera_info.k1 ... k3: this libmvo_hip.so has no mvo_undistort");
             printf("undistorting every image: k1 %g, k2 %g, p1 %g, p2 %g, k3 %g\n", dist[0], dist[1], dist[2], dist[3], dist[4]);
+        }
+        if (basics::Config::has("triangulation_match_by_epipolar_line") && basics::Config::get<int>("triangulation_match_by_epipolar_line") != 0) {
+            if (!mvo_fundamental_from_poses || !mvo_match_features_epipolar)
+                throw std::runtime_error("triangulation_match_by_epipolar_line: this libmvo_hip.so has no mvo_match_features_epipolar");
+            printf("keyframes are matched along the epipolar lines of their poses\n");
         }
         const int max_num_imgs_to_proc = basics::Config::get<int>("max_num_imgs_to_proc");
         const bool init_from_images = basics::Config::has("init_from_images") && basics::Config::get<int>("init_from_images") != 0;

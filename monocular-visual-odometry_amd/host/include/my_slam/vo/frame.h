@@ -39,6 +39,12 @@ public:
     vector<double> triangulation_angles_of_inliers_;
     std::unordered_map<int, PtConn> inliers_to_mappt_connections_;  // curr idx -> idx in ref, and map
     vector<cv::DMatch> matches_with_map_;
+    // (not in the reference) `triangulation_match_by_epipolar_line: 1`: the F that gated matches_with_ref_, the keyframe it
+    // was taken against and that keyframe's pose at that moment (the window BA of later frames moves a keyframe's T_w_c_
+    // after it was inserted); empty matrices otherwise
+    cv::Mat epipolar_F_;
+    cv::Mat epipolar_ref_T_w_c_;
+    int epipolar_ref_id_ = -1;
 
     // -- Current pose (cam -> world, see vo.cpp:31,89)
     cv::Mat T_w_c_;

@@ -4,6 +4,7 @@
 // (VisualOdometry::retainGoodTriangulationResult_, src/vo/vo.cpp:181-244).
 #ifndef MY_SLAM_KEYFRAME_H
 #define MY_SLAM_KEYFRAME_H
+#include "my_slam/geometry/epipolar_match.h"
 #include "my_slam/geometry/feature_match.h"
 #include "my_slam/geometry/motion_estimation.h"
 #include "my_slam/vo/frame.h"
@@ -56,13 +57,26 @@ inline void retainGoodTriangulationResult(const Frame::Ptr& curr, const Frame::P
     }
 }
 
-// vo_addFrame.cpp:96-118 up to (not including) pushCurrPointsToMap_
+// vo_addFrame.cpp:96-118 up to (not including) pushCurrPointsToMap_.  Optional key `triangulation_match_by_epipolar_line`
+// (0 / 1, default 0): 1 replaces the all-pairs matchFeatures of vo_addFrame.cpp:99 by the search along the epipolar lines
+// that the two known poses give (my_slam/geometry/epipolar_match.h; the reference's README.md:212,272); what follows it
+// is the same either way.
 inline void triangulateWithReferenceKeyframe(const Frame::Ptr& curr, const Frame::Ptr& ref, const cv::Mat& K) {
     static const float max_matching_pixel_dist_in_triangulation =
         basics::Config::get<float>("max_matching_pixel_dist_in_triangulation");
     static const int method_index = (int)basics::Config::get<float>("feature_match_method_index_pnp");
-    geometry::matchFeatures(ref->descriptors_, curr->descriptors_, curr->matches_with_ref_, method_index, false,
-                            ref->keypoints_, curr->keypoints_, max_matching_pixel_dist_in_triangulation);
+    static const bool by_epipolar_line = basics::Config::has("triangulation_match_by_epipolar_line") &&
+                                         basics::Config::get<int>("triangulation_match_by_epipolar_line") != 0;
+    if (by_epipolar_line) {
+        curr->epipolar_F_ = geometry::fundamentalFromPoses(ref->T_w_c_, curr->T_w_c_, K);
+        curr->epipolar_ref_id_ = ref->id_;
+        curr->epipolar_ref_T_w_c_ = ref->T_w_c_.clone();
+        geometry::matchFeaturesByEpipolarLine(ref->descriptors_, curr->descriptors_, ref->keypoints_, curr->keypoints_,
+                                              curr->epipolar_F_, curr->matches_with_ref_);
+    } else {
+        geometry::matchFeatures(ref->descriptors_, curr->descriptors_, curr->matches_with_ref_, method_index, false,
+                                ref->keypoints_, curr->keypoints_, max_matching_pixel_dist_in_triangulation);
+    }
     curr->inliers_matches_with_ref_ =
         geometry::helperFindInlierMatchesByEpipolarCons(ref->keypoints_, curr->keypoints_, curr->matches_with_ref_, K);
     curr->inliers_pts3d_ = geometry::helperTriangulatePoints(ref->keypoints_, curr->keypoints_, curr->inliers_matches_with_ref_,
