@@ -347,6 +347,53 @@ int mvo_map_points_in_view(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, doub
 int mvo_solve_pnp_ransac(mvo_ctx* ctx, const float* pts3d, const float* pts2d, int n, double fx, double fy,
                          double cx, double cy, int iterations, float reprojection_error, double confidence,
                          double* rvec, double* tvec, int32_t* inliers, int cap, int* n_inliers, int* found);
+/* ---- tracking by projection ----------------------------------------------------------------- */
+/* Pose-guided matching for the step that runs on every frame, poseEstimationPnP_ (vo.cpp:267-289), which in the
+ * reference projects the map with the LAST KEYFRAME's pose and then searches without a radius; README.md:212 names the
+ * remedy ("doing guided matching based on the estimated camera motion").  The resident map (mvo_map_*) is projected with
+ * T_w_c -- a prediction of the current pose, mvo_predict_pose -- and map point i (the query) competes for frame keypoint
+ * j (the train) only if j lies within its radius of i's projection.  Declared operation by operation in DESIGN.md
+ * section 15:
+ *   projection and in_view: the arithmetic of mvo_map_points_in_view, bit for bit (T_c_w by mvo_invert_pose)
+ *   du = (double)txy[j].x - (double)u, dv = (double)txy[j].y - (double)v, d2 = du du + dv dv
+ *   pass = in_view && d2 <= r2[j];   r2[j] = rj rj, rj = max_px * (t_scale ? (double)t_scale[j] : 1)
+ * The gate is inclusive, a NaN fails, there is no square root.  One launch (k_map_match_projection) per call; the map's
+ * positions and descriptors never leave HBM.
+ * MVO_ERR_INVALID: a null pointer with a positive count, a null map, a singular or non-finite pose, fx or fy 0, cols or
+ * rows <= 0, max_px negative or NaN, a t_scale entry negative or not finite.  MVO_ERR_CAPACITY: nt > 65535.  An empty
+ * map succeeds and writes nothing; nt == 0 succeeds (points in view: n_candidates 0, the others -1). */
+/* README.md:212, vo.cpp:267-289.  Raw: one row per map point, in the order of the uploaded arrays.  In view: px = its
+ * pixel, idx / dist = the two nearest gated keypoints in 256-bit Hamming space, equal distances keep the lower train
+ * index first, a missing neighbour is (-1, INT32_MAX), n_candidates = the number of keypoints that passed the gate.
+ * Not in view: px (0, 0), idx (-1, -1), dist (INT32_MAX, INT32_MAX), n_candidates -1.
+ * px (n_map x 2 f32) and n_candidates (n_map) are optional; idx / dist: n_map x 2 int32. */
+int mvo_map_match_knn2_projection(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx,
+                                  double cy, int cols, int rows, const uint8_t* t, const float* txy,
+                                  const float* t_scale /* nt or NULL */, int nt, double max_px, float* px, int32_t* idx,
+                                  int32_t* dist, int32_t* n_candidates);
+/* README.md:212, vo.cpp:267-289.  The same with the frame's descriptors already in HBM (the pointer
+ * mvo_calc_descriptors_dev returns); txy and t_scale stay host pointers. */
+int mvo_map_match_knn2_projection_dev(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx,
+                                      double cy, int cols, int rows, const void* d_t, const float* txy,
+                                      const float* t_scale, int nt, double max_px, float* px, int32_t* idx,
+                                      int32_t* dist, int32_t* n_candidates);
+/* README.md:212, vo.cpp:267-289.  The raw call followed by the filter of mvo_match_features_epipolar, unchanged: query
+ * i is kept if idx0 >= 0, d0 <= max_hamming and (idx1 < 0 or (double)d0 < lowe_ratio * (double)d1); one query per train
+ * survives (smallest distance, then the lower queryIdx); out is sorted by trainIdx, imgIdx 0, distance (float)d0;
+ * queryIdx is the MAP index.  px (n_map x 2) and in_view (n_map uint8) are optional.  MVO_ERR_CAPACITY (with *n set) if
+ * cap is too small. */
+int mvo_map_match_features_projection(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx,
+                                      double cy, int cols, int rows, const uint8_t* t, const float* txy,
+                                      const float* t_scale, int nt, double max_px, double lowe_ratio, int max_hamming,
+                                      float* px, uint8_t* in_view, mvo_dmatch* out, int cap, int* n);
+/* include/my_slam/vo/map.h:19 (map_points_.size(), of the resident copy).  The number of points the last mvo_map_upload
+ * left resident: the number of rows the three calls above write. */
+int mvo_map_size(mvo_ctx* ctx, mvo_map* map, int* n);
+/* README.md:212 ("based on the estimated camera motion"), vo.cpp:267-289.  Host-side, no ctx: the constant-velocity
+ * prediction D = inv(T_prev2) * T_prev, T_pred = T_prev * D of row-major 4 x 4 camera-to-world poses (inv =
+ * mvo_invert_pose, each product summed k = 0..3 in order, no re-orthonormalisation).  T_w_c_prev2 NULL: T_pred = T_prev.
+ * MVO_ERR_INVALID for a singular T_prev2. */
+int mvo_predict_pose(const double* T_w_c_prev2 /* or NULL */, const double* T_w_c_prev, double* T_w_c_pred);
 /* ---- keyframe insertion: epipolar inlier filter, triangulation, culling ---- */
 /* geometry::helperTriangulatePoints (src/geometry/motion_estimation.cpp:214-247, called at
  * vo_addFrame.cpp:114-116): pixel2CamNormPlane on the matched pixels of the previous / current keyframe

@@ -366,6 +366,67 @@ class Context:
                                                        _p(out), cap, C.byref(n)))
         return out[:n.value].copy()
 
+    # ---- tracking by projection (README.md:212 of the reference; the step of vo.cpp:267-289)
+    @staticmethod
+    def _projection_args(T_w_c, K, txy, t_scale):
+        T = np.ascontiguousarray(T_w_c, np.float64).reshape(16)
+        txy = np.ascontiguousarray(txy, np.float32).reshape(-1, 2)
+        if t_scale is not None:
+            t_scale = np.ascontiguousarray(t_scale, np.float32).reshape(-1)
+            if len(t_scale) != len(txy):
+                raise ValueError("t_scale needs one entry per frame keypoint")
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        return T, k, txy, t_scale
+
+    def _map_size(self, m):
+        """Number of points of the resident map (the outputs of the projection calls have one row each)."""
+        n = C.c_int()
+        self._chk(self.lib.mvo_map_size(self.h, m, C.byref(n)))
+        return n.value
+
+    def map_match_knn2_projection(self, m, T_w_c, K, cols, rows, t, txy, max_px, t_scale=None):
+        """mvo_map_match_knn2_projection: per map point its pixel under T_w_c and the two nearest frame keypoints within
+        t_scale[j] * max_px of it -> (px n_map x 2 f32, idx n_map x 2, dist n_map x 2, n_candidates n_map; -1: not in view)."""
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        T, k, txy, t_scale = self._projection_args(T_w_c, K, txy, t_scale)
+        if len(txy) != len(t):
+            raise ValueError("one keypoint position per descriptor")
+        n = self._map_size(m)
+        px, idx, dist = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32)
+        cnt = np.zeros(n, np.int32)
+        self._chk(self.lib.mvo_map_match_knn2_projection(self.h, m, _p(T), *k, int(cols), int(rows), _p(t), _p(txy), _p(t_scale),
+                                                         len(t), C.c_double(max_px), _p(px), _p(idx), _p(dist), _p(cnt)))
+        return px, idx, dist, cnt
+
+    def map_match_knn2_projection_dev(self, m, T_w_c, K, cols, rows, d_t, txy, max_px, t_scale=None):
+        """The same with the frame's descriptors in HBM (a device pointer); the count comes from txy."""
+        T, k, txy, t_scale = self._projection_args(T_w_c, K, txy, t_scale)
+        n = self._map_size(m)
+        px, idx, dist = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32)
+        cnt = np.zeros(n, np.int32)
+        self._chk(self.lib.mvo_map_match_knn2_projection_dev(self.h, m, _p(T), *k, int(cols), int(rows), C.c_void_p(d_t), _p(txy),
+                                                             _p(t_scale), len(txy), C.c_double(max_px), _p(px), _p(idx), _p(dist),
+                                                             _p(cnt)))
+        return px, idx, dist, cnt
+
+    def map_match_features_projection(self, m, T_w_c, K, cols, rows, t, txy, max_px, lowe_ratio, max_hamming, t_scale=None,
+                                      cap=None):
+        """mvo_map_match_features_projection: the raw call, the ceiling / ratio filter, one map point per keypoint ->
+        (DMATCH_DTYPE sorted by trainIdx with queryIdx = map index, px n_map x 2, in_view n_map bool)."""
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        T, k, txy, t_scale = self._projection_args(T_w_c, K, txy, t_scale)
+        if len(txy) != len(t):
+            raise ValueError("one keypoint position per descriptor")
+        n = self._map_size(m)
+        cap = min(n, len(t)) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        px, in_view = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+        cnt = C.c_int()
+        self._chk(self.lib.mvo_map_match_features_projection(self.h, m, _p(T), *k, int(cols), int(rows), _p(t), _p(txy), _p(t_scale),
+                                                             len(t), C.c_double(max_px), C.c_double(lowe_ratio), int(max_hamming),
+                                                             _p(px), _p(in_view), _p(out), cap, C.byref(cnt)))
+        return out[:cnt.value].copy(), px, in_view.astype(bool)
+
     # ---- bundle adjustment
     def _ba_problem(self, poses, points, edge_pose, edge_point, edge_uv, focal, cx, cy, info, huber_delta,
                     fix_points, pose_fixed, max_iterations):
@@ -846,6 +907,18 @@ def fundamental_from_poses(T_w_c_1, T_w_c_2, K):
     if r != MVO_OK:
         raise MvoError(r, "mvo_fundamental_from_poses: singular pose or fx / fy 0")
     return F.reshape(3, 3)
+
+
+def predict_pose(T_w_c_prev2, T_w_c_prev):
+    """mvo_predict_pose: T_prev * (inv(T_prev2) * T_prev), the constant-velocity prediction of the next camera-to-world pose
+    (4 x 4); T_w_c_prev2 None: T_prev.  Host-side, needs no GPU."""
+    T2 = None if T_w_c_prev2 is None else np.ascontiguousarray(T_w_c_prev2, np.float64).reshape(16)
+    T1 = np.ascontiguousarray(T_w_c_prev, np.float64).reshape(16)
+    out = np.zeros(16)
+    r = load_library().mvo_predict_pose(_p(T2), _p(T1), _p(out))
+    if r != MVO_OK:
+        raise MvoError(r, "mvo_predict_pose: singular T_w_c_prev2")
+    return out.reshape(4, 4)
 
 
 def retain_good_triangulation(pts3d_in_curr, T_w_c_curr, T_w_c_ref, min_triang_angle=1.0, max_ratio_to_median=20.0):

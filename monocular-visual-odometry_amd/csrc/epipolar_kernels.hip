@@ -92,6 +92,7 @@ __global__ __launch_bounds__(256) void k_knn2_epipolar(const uint4* __restrict__
             __hip_atomic_store(part_cnt + ((size_t)blockIdx.y * nq + qi), cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         MVO_WAIT_VM0();  // the write-through stores are complete before this workgroup is counted
+        __builtin_amdgcn_wave_barrier();  // ... those of EVERY lane: lane 0 counts the workgroup only after all 64 have stored
         int last = 0;
         if (lane == 0) {
             last = __hip_atomic_fetch_add(arrive + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ngroups - 1;

@@ -105,6 +105,7 @@ __global__ __launch_bounds__(256) void k_knn2(const uint4* __restrict__ q, int n
         __hip_atomic_store(mine + 1, ((u64)(uint32_t)p.w << 32) | (uint32_t)p.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     MVO_WAIT_VM0();  // the write-through stores are complete before this workgroup is counted
+    __builtin_amdgcn_wave_barrier();  // ... those of EVERY lane: lane 0 counts the workgroup only after all 64 have stored
     int last = 0;
     if (lane == 0) {
         last = __hip_atomic_fetch_add(arrive + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == MK_GROUPS - 1;

@@ -159,6 +159,11 @@ struct TrackViewArgs {
     int cols, rows;
 };
 struct mvo_track_state;  // device buffers of the tracking rows, allocated on first use
+struct mvo_map {  // the resident map (mvo_map_*, track_host.cpp): n x 3 f32 positions, n x 32 descriptor bytes
+    float* d_pos = nullptr;
+    uint8_t* d_desc = nullptr;
+    int n = 0, cap = 0;
+};
 
 // undistortion (undistort_kernels.hip / undistort_host.cpp)
 struct UndistortArgs {  // k_undistort_map: the model with 1 / fx, 1 / fy taken on the host, missing coefficients 0
@@ -193,6 +198,16 @@ struct mvo_epipolar_state {  // owned by epipolar_host.cpp, released through mvo
     int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
     int32_t* d_out = nullptr;  // cap_q x 5: where a caller that keeps the result on the device has it delivered
     int cap_q = 0, cap_t = 0;
+};
+
+// tracking by projection (projection_kernels.hip / projection_host.cpp)
+#define PK_MAX_GROUPS 8  // train groups of k_map_match_projection (workgroups per group of 64 map points)
+struct mvo_projection_state {  // owned by projection_host.cpp, released through mvo_ctx::proj_release
+    uint8_t* d_t = nullptr;   // staging of the host-pointer form
+    double* d_tg = nullptr;   // cap_t x ((double)x, (double)y, r2): the gate's view of the frame keypoints
+    unsigned long long* d_part = nullptr;  // PK_MAX_GROUPS x cap_m partial key pairs, then as many counts, then the arrival counters
+    int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
+    int cap_m = 0, cap_t = 0;
 };
 
 struct ProfEntry {
@@ -275,6 +290,9 @@ struct mvo_ctx {
     // --- pose-guided matching: allocated by the first mvo_match_knn2_epipolar*, released like the undistortion
     mvo_epipolar_state* epi = nullptr;
     void (*epi_release)(mvo_ctx*) = nullptr;
+    // --- tracking by projection: allocated by the first mvo_map_match_knn2_projection*, released like the undistortion
+    mvo_projection_state* proj = nullptr;
+    void (*proj_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -368,6 +386,10 @@ int epipolar_groups(int nt);
 int epipolar_launch_knn2(mvo_ctx* ctx, const uint8_t* d_q, const float* d_qxy, int nq, const uint8_t* d_t, const float* d_txy,
                          const double* d_tol2, int nt, const EpipolarArgs& a, unsigned long long* d_part, int32_t* d_part_cnt,
                          int32_t* d_arrive, int32_t* out);
+// projection_kernels.hip
+int projection_groups(int nt);
+int projection_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, int n_map, const TrackViewArgs& a, const uint8_t* d_t,
+                      const double* d_tg, int nt, unsigned long long* d_part, int32_t* d_part_cnt, int32_t* d_arrive, int32_t* out);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -1,0 +1,221 @@
+// csrc/projection_host.cpp -- host side of tracking by projection (include/mvo_hip.h: mvo_map_match_knn2_projection,
+// mvo_map_match_knn2_projection_dev, mvo_map_match_features_projection, mvo_map_size, mvo_predict_pose): argument checks, the per-keypoint
+// radius, staging, the filter and the one-query-per-train rule.  The kernel is in projection_kernels.hip, the arithmetic in
+// DESIGN.md section 15.  No other translation unit refers to this one: mvo_destroy reaches projection_release through
+// mvo_ctx::proj_release.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "mvo_internal.h"
+
+namespace {
+
+const int kMaxTrains = 65535;  // the train index lives in the low 16 bits of a key
+
+void projection_release(mvo_ctx* ctx) {
+    mvo_projection_state* e = ctx->proj;
+    if (!e) return;
+    void* dev[] = {e->d_t, e->d_tg, e->d_part};
+    for (void* p : dev)
+        if (p) mvo_free_on_current_device(p);
+    delete e;
+    ctx->proj = nullptr;
+}
+
+int ensure_bufs(mvo_ctx* ctx, int n_map, int nt) {
+    if (!ctx->proj) {
+        ctx->proj = new mvo_projection_state();
+        ctx->proj_release = projection_release;
+    }
+    mvo_projection_state* e = ctx->proj;
+    if (n_map > e->cap_m) {
+        if (e->d_part) mvo_free_on_current_device(e->d_part);
+        e->d_part = nullptr;
+        e->cap_m = 0;
+        const size_t cap = (size_t)std::max(4096, n_map + n_map / 2);
+        // partial key pairs, partial counts, one arrival counter per group of 64 map points (self re-arming, zeroed once)
+        const size_t keys = PK_MAX_GROUPS * cap * 8, cnts = PK_MAX_GROUPS * cap * 4, ctr = (cap / 64 + 2) * 4;
+        MVO_HIP(hipMalloc((void**)&e->d_part, keys + cnts + ctr));
+        e->d_part_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys);
+        e->d_arrive = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys + cnts);
+        MVO_HIP(hipMemsetAsync(e->d_arrive, 0, ctr, ctx->stream));
+        e->cap_m = (int)cap;
+    }
+    if (nt > e->cap_t) {
+        void* old[] = {e->d_t, e->d_tg};
+        for (void* p : old)
+            if (p) mvo_free_on_current_device(p);
+        e->d_t = nullptr, e->d_tg = nullptr;
+        e->cap_t = 0;
+        const size_t cap = (size_t)std::max(4096, nt + nt / 2);
+        MVO_HIP(hipMalloc((void**)&e->d_t, cap * 32));
+        MVO_HIP(hipMalloc((void**)&e->d_tg, cap * 24));
+        e->cap_t = (int)cap;
+    }
+    return MVO_OK;
+}
+
+inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
+
+// Every form: the checks, the upload, the launch, the results.  t is a host pointer (t_on_device false) or a device pointer.
+int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy, int cols, int rows,
+        const void* t, bool t_on_device, const float* txy, const float* t_scale, int nt, double max_px, float* px, int32_t* idx,
+        int32_t* dist, int32_t* n_candidates, const char* who) {
+    if (!ctx) return MVO_ERR_INVALID;
+    auto invalid = [&](const char* what, int code = MVO_ERR_INVALID) {  // the message names the entry point the caller used
+        return mvo_set_err(ctx, code, (std::string(who) + ": " + what).c_str(), hipSuccess);
+    };
+    if (!map || !T_w_c || nt < 0 || (nt && (!t || !txy)) || (map->n && (!idx || !dist)))
+        return invalid("bad arguments");
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(T_w_c[k])) return invalid("T_w_c is not finite");
+    double Ti[16];
+    if (mvo_invert_pose(T_w_c, Ti) != MVO_OK)
+        return invalid("T_w_c is singular");
+    if (fx == 0 || fy == 0 || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return invalid("fx or fy 0, or intrinsics not finite");
+    if (cols <= 0 || rows <= 0) return invalid("cols or rows <= 0");
+    if (!(max_px >= 0)) return invalid("max_px negative or NaN");
+    if (nt > kMaxTrains) return invalid("more than 65535 train descriptors", MVO_ERR_CAPACITY);
+    if (t_scale)
+        for (int j = 0; j < nt; ++j)
+            if (!std::isfinite(t_scale[j]) || t_scale[j] < 0)
+                return invalid("t_scale entry negative or not finite");
+    const int n_map = map->n;
+    if (n_map == 0) return MVO_OK;
+    TrackViewArgs a;
+    std::memcpy(a.T, Ti, sizeof a.T);
+    a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
+    a.cols = cols, a.rows = rows;
+    MVO_HIP(hipSetDevice(ctx->device));
+    int r = ensure_bufs(ctx, n_map, nt);
+    if (r) return r;
+    mvo_projection_state* e = ctx->proj;
+    // pinned staging: the kernel writes its n_map x 28 bytes of results straight into the first part; the second carries the
+    // gate's view of the frame keypoints up (one copy)
+    const size_t out_bytes = align64((size_t)n_map * 28);
+    if ((r = mvo_ensure_pinned(ctx, out_bytes + (size_t)nt * 24))) return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
+    int32_t* h_out = reinterpret_cast<int32_t*>(ctx->h_pin);
+    double* h_tg = reinterpret_cast<double*>(ctx->h_pin + out_bytes);
+    for (int j = 0; j < nt; ++j) {
+        const double rj = max_px * (t_scale ? (double)t_scale[j] : 1.0);
+        h_tg[3 * j] = (double)txy[2 * j];
+        h_tg[3 * j + 1] = (double)txy[2 * j + 1];
+        h_tg[3 * j + 2] = rj * rj;
+    }
+    const uint8_t* d_t = static_cast<const uint8_t*>(t);
+    if (nt) {
+        MVO_HIP(hipMemcpyAsync(e->d_tg, h_tg, (size_t)nt * 24, hipMemcpyHostToDevice, ctx->stream));
+        if (!t_on_device) {
+            MVO_HIP(hipMemcpyAsync(e->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
+            d_t = e->d_t;
+        }
+    }
+    ExtractGate gate(ctx);
+    if ((r = projection_launch(ctx, map->d_pos, map->d_desc, n_map, a, d_t, e->d_tg, nt, e->d_part, e->d_part_cnt, e->d_arrive, h_out)))
+        return r;
+    MVO_HIP(hipStreamSynchronize(ctx->stream));
+    gate.release();
+    if (ctx->prof) mvo_prof_collect(ctx);
+    std::memcpy(idx, ctx->h_pin, (size_t)n_map * 8);
+    std::memcpy(dist, ctx->h_pin + (size_t)n_map * 8, (size_t)n_map * 8);
+    if (px) std::memcpy(px, ctx->h_pin + (size_t)n_map * 16, (size_t)n_map * 8);
+    if (n_candidates) std::memcpy(n_candidates, ctx->h_pin + (size_t)n_map * 24, (size_t)n_map * 4);
+    return MVO_OK;
+}
+
+// D = A * B, row-major 4 x 4, summed k = 0..3 in order
+void mul4(const double* A, const double* B, double* D) {
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double s = 0;
+            for (int k = 0; k < 4; ++k) s += A[4 * i + k] * B[4 * k + j];
+            D[4 * i + j] = s;
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+// README.md:212 ("doing guided matching based on the estimated camera motion"), vo.cpp:267-289 (the step it replaces:
+// getMappointsInCurrentView_ + matchFeatures in poseEstimationPnP_)
+int mvo_map_match_knn2_projection(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy,
+                                  int cols, int rows, const uint8_t* t, const float* txy, const float* t_scale, int nt, double max_px,
+                                  float* px, int32_t* idx, int32_t* dist, int32_t* n_candidates) {
+    return run(ctx, map, T_w_c, fx, fy, cx, cy, cols, rows, t, false, txy, t_scale, nt, max_px, px, idx, dist, n_candidates,
+               "mvo_map_match_knn2_projection");
+}
+
+// README.md:212, vo.cpp:267-289: the same with the frame's descriptors already in HBM
+int mvo_map_match_knn2_projection_dev(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy,
+                                      int cols, int rows, const void* d_t, const float* txy, const float* t_scale, int nt,
+                                      double max_px, float* px, int32_t* idx, int32_t* dist, int32_t* n_candidates) {
+    return run(ctx, map, T_w_c, fx, fy, cx, cy, cols, rows, d_t, true, txy, t_scale, nt, max_px, px, idx, dist, n_candidates,
+               "mvo_map_match_knn2_projection_dev");
+}
+
+// README.md:212, vo.cpp:267-289: the raw call, the filter, one query per train
+int mvo_map_match_features_projection(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy,
+                                      int cols, int rows, const uint8_t* t, const float* txy, const float* t_scale, int nt,
+                                      double max_px, double lowe_ratio, int max_hamming, float* px, uint8_t* in_view, mvo_dmatch* out,
+                                      int cap, int* n) {
+    if (!ctx) return MVO_ERR_INVALID;
+    if (!n || !map || cap < 0) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_map_match_features_projection: bad arguments", hipSuccess);
+    *n = 0;
+    const int n1 = map->n;
+    std::vector<int32_t> idx(2 * (size_t)n1 + 2), dist(2 * (size_t)n1 + 2), cand((size_t)n1 + 1);
+    int r = run(ctx, map, T_w_c, fx, fy, cx, cy, cols, rows, t, false, txy, t_scale, nt, max_px, px, idx.data(), dist.data(), cand.data(),
+                "mvo_map_match_features_projection");
+    if (r) return r;
+    if (in_view)
+        for (int i = 0; i < n1; ++i) in_view[i] = cand[i] >= 0 ? 1 : 0;
+    // per train the claiming query with the smallest (distance, queryIdx); queries arrive in ascending order
+    std::vector<int32_t> owner(nt > 0 ? nt : 1, -1);
+    for (int i = 0; i < n1; ++i) {
+        const int j = idx[2 * i], d0 = dist[2 * i];
+        if (j < 0 || d0 > max_hamming) continue;
+        if (idx[2 * i + 1] >= 0 && !((double)d0 < lowe_ratio * (double)dist[2 * i + 1])) continue;
+        if (owner[j] < 0 || d0 < dist[2 * owner[j]]) owner[j] = i;
+    }
+    int cnt = 0;
+    for (int j = 0; j < nt; ++j) cnt += owner[j] >= 0 ? 1 : 0;
+    *n = cnt;
+    if (cnt > cap || (cnt && !out)) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "match buffer too small", hipSuccess);
+    int k = 0;
+    for (int j = 0; j < nt; ++j)
+        if (owner[j] >= 0) out[k++] = {owner[j], j, 0, (float)dist[2 * owner[j]]};
+    return MVO_OK;
+}
+
+// map.h:19 (Map::map_points_.size() of the resident copy): the number of rows the calls above write
+int mvo_map_size(mvo_ctx* ctx, mvo_map* map, int* n) {
+    if (!ctx) return MVO_ERR_INVALID;
+    if (!map || !n) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_map_size: bad arguments", hipSuccess);
+    *n = map->n;
+    return MVO_OK;
+}
+
+// README.md:212 ("based on the estimated camera motion"), vo.cpp:267-289: the constant-velocity prediction of the pose the
+// map is projected with, T_pred = T_prev * (inv(T_prev2) * T_prev)
+int mvo_predict_pose(const double* T_w_c_prev2, const double* T_w_c_prev, double* T_w_c_pred) {
+    if (!T_w_c_prev || !T_w_c_pred) return MVO_ERR_INVALID;
+    double out[16];
+    if (!T_w_c_prev2) {
+        std::memcpy(out, T_w_c_prev, sizeof out);
+    } else {
+        double Ti[16], D[16];
+        if (mvo_invert_pose(T_w_c_prev2, Ti) != MVO_OK) return MVO_ERR_INVALID;
+        mul4(Ti, T_w_c_prev, D);
+        mul4(T_w_c_prev, D, out);
+    }
+    std::memcpy(T_w_c_pred, out, sizeof out);
+    return MVO_OK;
+}
+
+}  // extern "C"

@@ -9,12 +9,6 @@
 
 #include "mvo_internal.h"
 
-struct mvo_map {
-    float* d_pos = nullptr;
-    uint8_t* d_desc = nullptr;
-    int n = 0, cap = 0;
-};
-
 struct mvo_track_state {
     // PnP: pairs, subsets, per-hypothesis results, refinement scratch
     double *d_Mg = nullptr, *d_mg = nullptr;

@@ -31,6 +31,15 @@
 // after MREF: EPIF = int32 id_ of the reference keyframe, int32 0, the 9 f64 of F (x_curr^T F x_ref = 0), row-major; and
 // EPIR = the 16 f64 of the reference keyframe's T_w_c_ as F was computed from it (its POSE record dates from its own frame;
 // the window bundle adjustment of the frames since has moved it).  F = mvo_fundamental_from_poses(EPIR, this frame's POSE).
+// Optional key `tracking_match_by_projection` (0 / 1, default 0): 1 makes every tracked frame start from a constant-velocity
+// prediction of its pose (from the last two frames) instead of the last keyframe's, project the resident map with it and match
+// each point in view within a radius of its projection (my_slam/vo/projection_match.h; the reference's README.md:212) instead
+// of getMappointsInCurrentView_ + matchFeatures (vo.cpp:267-289).  Its three parameters, optional as well:
+// `projection_match_max_pixel_dist` (px at pyramid level 0, default 8.0), `projection_match_lowe_ratio` (default 0.8),
+// `projection_match_max_hamming` (default 64).  With the key on, a tracked frame's part of the frame log carries five more
+// records after MORD: PRVP = the 32 f64 of T_prev2 and T_prev as used (T_prev twice without a prev2), PRED = the 16 f64 of
+// the predicted pose, PPOS / PDSC = the map's positions (n x 3 f32) and descriptors (n x 32) as uploaded, in MORD order,
+// MPRJ = the matches handed to PnP before the inlier selection (queryIdx -> index among the points in view).
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -56,6 +65,9 @@
 // ... or without the pose-guided matcher (`triangulation_match_by_epipolar_line`): an error, not a fall-back
 #pragma weak mvo_fundamental_from_poses
 #pragma weak mvo_match_features_epipolar
+// ... or without tracking by projection (`tracking_match_by_projection`): likewise
+#pragma weak mvo_predict_pose
+#pragma weak mvo_map_match_features_projection
 
 using namespace my_slam;
 
@@ -88,6 +100,15 @@ struct FrameLog {
         vector<int> order;
         for (const vo::MapPoint::Ptr& p : dev_map.order()) order.push_back(p->id_);
         vec("MORD", order);  // iteration order of Map::map_points_ when the frame looked at the map
+        if (!fr->projection_pred_T_.empty()) {  // `tracking_match_by_projection: 1`: what the matcher saw
+            vec("PRVP", fr->projection_prev_T_);
+            double T[16];
+            for (int i = 0; i < 16; ++i) T[i] = fr->projection_pred_T_.at<double>(i / 4, i % 4);
+            put("PRED", T, sizeof T);
+            vec("PPOS", fr->projection_map_pos_);
+            vec("PDSC", fr->projection_map_desc_);
+            vec("MPRJ", fr->projection_matches_);
+        }
         vec("MMAP", fr->matches_with_map_);  // the PnP inliers' matches (vo.cpp:336-349)
         const int flags[2] = {good ? 1 : 0, is_keyframe ? 1 : 0};
         put("FLAG", flags, sizeof flags);
@@ -218,6 +239,11 @@ int main(int argc, char** argv) {
             if (!mvo_fundamental_from_poses || !mvo_match_features_epipolar)
                 throw std::runtime_error("triangulation_match_by_epipolar_line: this libmvo_hip.so has no mvo_match_features_epipolar");
             printf("keyframes are matched along the epipolar lines of their poses\n");
+        }
+        if (vo::trackingMatchByProjection()) {
+            if (!mvo_predict_pose || !mvo_map_match_features_projection)
+                throw std::runtime_error("tracking_match_by_projection: this libmvo_hip.so has no mvo_map_match_features_projection");
+            printf("frames are tracked by projection of the map with a predicted pose\n");
         }
         const int max_num_imgs_to_proc = basics::Config::get<int>("max_num_imgs_to_proc");
         const bool init_from_images = basics::Config::has("init_from_images") && basics::Config::get<int>("init_from_images") != 0;

@@ -45,6 +45,15 @@ public:
     cv::Mat epipolar_F_;
     cv::Mat epipolar_ref_T_w_c_;
     int epipolar_ref_id_ = -1;
+    // (not in the reference) `tracking_match_by_projection: 1`: what the matcher of poseEstimationPnP saw -- the two poses the
+    // prediction was made from (32 f64: T_prev2 then T_prev, T_prev twice without a prev2), the predicted pose, the map's
+    // positions (n x 3) and descriptors (n x 32) as uploaded, and the matches handed to PnP before the inlier selection.  The
+    // bundle adjustment rewrites poses and positions in place afterwards; empty otherwise
+    vector<double> projection_prev_T_;
+    cv::Mat projection_pred_T_;
+    vector<float> projection_map_pos_;
+    vector<unsigned char> projection_map_desc_;
+    vector<cv::DMatch> projection_matches_;
 
     // -- Current pose (cam -> world, see vo.cpp:31,89)
     cv::Mat T_w_c_;

@@ -114,6 +114,8 @@ public:
     mvo_map* handle() const { return map_; }
     const vector<MapPoint::Ptr>& order() const { return order_; }
     const unsigned char* descriptor(int i) const { return &desc_[32 * (size_t)i]; }
+    const vector<float>& positions() const { return pos_; }            // n x 3, as uploaded by the last sync()
+    const vector<unsigned char>& descriptors() const { return desc_; }  // n x 32
 
 private:
     mvo_map* map_ = nullptr;
@@ -153,6 +155,15 @@ inline void getMappointsInCurrentView(MapOnDevice& dev_map, const Map::Ptr& map,
     }
 }
 
+// my_slam/vo/projection_match.h (included at the end of this header): the matcher of `tracking_match_by_projection: 1`
+inline void matchMapByProjection(MapOnDevice& dev_map, const Map::Ptr& map, const Frame::Ptr& curr, const cv::Mat& K,
+                                 vector<MapPoint::Ptr>& candidate_mappoints_in_map, vector<cv::Point2f>& candidate_2d_pts_in_image,
+                                 vector<cv::DMatch>& matches);
+inline bool trackingMatchByProjection() {  // the optional key, latched on first use
+    static const bool on = basics::Config::has("tracking_match_by_projection") && basics::Config::get<int>("tracking_match_by_projection") != 0;
+    return on;
+}
+
 // VisualOdometry::poseEstimationPnP_ (vo.cpp:270-383): matches the map points in view against the frame, solves
 // PnP with RANSAC, records the inlier connections and sets curr->T_w_c_.  Returns is_pnp_good.
 inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const Frame::Ptr& curr, const Frame::Ptr& prev,
@@ -160,15 +171,20 @@ inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const F
     vector<MapPoint::Ptr> candidate_mappoints_in_map;
     vector<cv::Point2f> candidate_2d_pts_in_image;
     cv::Mat corresponding_mappoints_descriptors;
-    getMappointsInCurrentView(dev_map, map, curr, K, candidate_mappoints_in_map, candidate_2d_pts_in_image,
-                              corresponding_mappoints_descriptors);
-    vector<cv::KeyPoint> candidate_2d_kpts_in_image;  // geometry::pts2Keypts (feature_match.cpp:293-303)
-    for (const cv::Point2f& pt : candidate_2d_pts_in_image) candidate_2d_kpts_in_image.push_back(cv::KeyPoint(pt, 10));
+    if (trackingMatchByProjection()) {
+        // curr->T_w_c_ is the PREDICTED pose (trackFrame): the map is projected with it and matched in the same launch
+        matchMapByProjection(dev_map, map, curr, K, candidate_mappoints_in_map, candidate_2d_pts_in_image, curr->matches_with_map_);
+    } else {
+        getMappointsInCurrentView(dev_map, map, curr, K, candidate_mappoints_in_map, candidate_2d_pts_in_image,
+                                  corresponding_mappoints_descriptors);
+        vector<cv::KeyPoint> candidate_2d_kpts_in_image;  // geometry::pts2Keypts (feature_match.cpp:293-303)
+        for (const cv::Point2f& pt : candidate_2d_pts_in_image) candidate_2d_kpts_in_image.push_back(cv::KeyPoint(pt, 10));
 
-    static const float max_matching_pixel_dist_in_pnp = basics::Config::get<float>("max_matching_pixel_dist_in_pnp");
-    static const int method_index = (int)basics::Config::get<float>("feature_match_method_index_pnp");
-    geometry::matchFeatures(corresponding_mappoints_descriptors, curr->descriptors_, curr->matches_with_map_, method_index,
-                            false, candidate_2d_kpts_in_image, curr->keypoints_, max_matching_pixel_dist_in_pnp);
+        static const float max_matching_pixel_dist_in_pnp = basics::Config::get<float>("max_matching_pixel_dist_in_pnp");
+        static const int method_index = (int)basics::Config::get<float>("feature_match_method_index_pnp");
+        geometry::matchFeatures(corresponding_mappoints_descriptors, curr->descriptors_, curr->matches_with_map_, method_index,
+                                false, candidate_2d_kpts_in_image, curr->keypoints_, max_matching_pixel_dist_in_pnp);
+    }
     const int num_matches = (int)curr->matches_with_map_.size();
     vector<cv::Point3f> pts_3d;
     vector<cv::Point2f> pts_2d;
@@ -209,6 +225,8 @@ inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const F
 
 }  // namespace vo
 }  // namespace my_slam
+
+#include "my_slam/vo/projection_match.h"
 
 #ifndef MVO_HAVE_OPENCV
 namespace cv {

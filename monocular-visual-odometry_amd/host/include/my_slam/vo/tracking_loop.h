@@ -20,6 +20,7 @@ struct TrackingState {  // the members of VisualOdometry the tracking branch tou
     MapOnDevice dev_map_;
     std::deque<Frame::Ptr> frames_buff_;
     Frame::Ptr ref_, prev_;
+    Frame::Ptr prev2_;  // the frame before prev_ (`tracking_match_by_projection: 1`: the constant-velocity prediction)
     double map_point_erase_ratio_ = 0.1;  // the function-local static of optimizeMap_
     static constexpr size_t kBuffSize_ = 20;
     void pushFrameToBuff(Frame::Ptr frame) {
@@ -120,8 +121,20 @@ inline void optimizeMap(TrackingState& st, const Frame::Ptr& curr, const cv::Mat
 inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat& K, bool* is_keyframe = nullptr) {
     st.pushFrameToBuff(curr);
     if (is_keyframe) *is_keyframe = false;
-    curr->T_w_c_ = st.ref_->T_w_c_.clone();  // Initial estimation of the current pose
     if (!st.prev_) st.prev_ = st.ref_;
+    if (trackingMatchByProjection()) {  // the pose predicted from the last two frames in place of the last keyframe's
+        // (a prev2 with the very pose of prev -- a frame whose PnP failed takes its predecessor's -- is no motion: as without a
+        // prev2 the prediction is T_prev itself, not T_prev * (inv(T_prev) * T_prev))
+        cv::Mat prev2 = st.prev2_ ? st.prev2_->T_w_c_ : cv::Mat();
+        if (!prev2.empty() && std::memcmp(prev2.ptr<double>(0), st.prev_->T_w_c_.ptr<double>(0), 16 * sizeof(double)) == 0) prev2 = cv::Mat();
+        curr->T_w_c_ = predictPose(prev2, st.prev_->T_w_c_);
+        curr->projection_prev_T_.clear();
+        for (const cv::Mat& T : {prev2.empty() ? st.prev_->T_w_c_ : prev2, st.prev_->T_w_c_})
+            for (int i = 0; i < 16; ++i) curr->projection_prev_T_.push_back(T.at<double>(i / 4, i % 4));
+        curr->projection_pred_T_ = curr->T_w_c_.clone();
+    } else {
+        curr->T_w_c_ = st.ref_->T_w_c_.clone();  // Initial estimation of the current pose
+    }
     const bool is_pnp_good = poseEstimationPnP(st.dev_map_, st.map_, curr, st.prev_, K);
     if (is_pnp_good) {
         callBundleAdjustment(st.frames_buff_, st.map_, K);
@@ -134,6 +147,7 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
             if (is_keyframe) *is_keyframe = true;
         }
     }
+    if (st.prev_ != curr) st.prev2_ = st.prev_;
     st.prev_ = curr;
     return is_pnp_good;
 }
