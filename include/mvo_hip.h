@@ -97,6 +97,35 @@ int mvo_calc_keypoints(mvo_ctx* ctx, const uint8_t* image, int width, int height
 /* Same with the image already resident in HBM (bench: inputs resident when the timed region starts). */
 int mvo_calc_keypoints_dev(mvo_ctx* ctx, const void* d_image, int width, int height, int stride,
                            int channels, mvo_keypoint* kps, int cap, int* n);
+/* ---- extraction, the ORB-SLAM way (README.md section 5: "use the ORB-SLAM's method for extracting enough uniformly
+ * distributed keypoints across different scales"; the reference names the method and has no function for it).  A second
+ * detector next to mvo_calc_keypoints*, chosen per call; the arithmetic is declared in DESIGN.md section 16: FAST-9/16 scored
+ * cell by cell (cells of about cell_size px inside the edge_threshold border) with 3 x 3 non-maximum suppression per cell, a
+ * cell keeping its corners of score >= ini_threshold or, if it has none, those >= min_threshold; per level a quadtree that
+ * splits the candidates until the level's quota of leaves is reached and keeps the best-scored candidate of every leaf; the
+ * intensity-centroid angle for the kept points.  Pyramid, per-level scale and quota are those of mvo_orb_configure;
+ * fast_threshold is not used.  response = the FAST score. */
+typedef struct {
+    int32_t ini_threshold;  /* 1..255, default 20 */
+    int32_t min_threshold;  /* 1..ini_threshold, default 7 */
+    int32_t cell_size;      /* 8..32, default 30 (a cell row is one 64-bit lane mask on the device: cells span < 2 * cell_size) */
+    int32_t edge_threshold; /* 19..31, default 19 */
+} mvo_orb_distribute_params;
+/* params == NULL restores the defaults.  MVO_ERR_INVALID for a value outside the ranges above. */
+int mvo_orb_distribute_configure(mvo_ctx* ctx, const mvo_orb_distribute_params* params);
+/* Arguments, limits and the cached pyramid as for mvo_calc_keypoints; selectUniformKptsByGrid follows as there.  A level too
+ * small for one cell yields no keypoints.  Up to two keypoints more than its quota can come from a level. */
+int mvo_calc_keypoints_distributed(mvo_ctx* ctx, const uint8_t* image, int width, int height, int stride,
+                                   int channels, mvo_keypoint* kps, int cap, int* n);
+int mvo_calc_keypoints_distributed_dev(mvo_ctx* ctx, const void* d_image, int width, int height, int stride,
+                                       int channels, mvo_keypoint* kps, int cap, int* n);
+/* The candidates of the last mvo_calc_keypoints_distributed* in their declared order (level, cell row, cell column, y, x),
+ * level coordinates.  out == NULL only queries the count. */
+typedef struct {
+    int32_t x, y, level, score;
+} mvo_distribute_candidate;
+int mvo_debug_get_distribute_candidates(mvo_ctx* ctx, mvo_distribute_candidate* out, int cap, int* n);
+
 /* geometry::calcDescriptors (feature_match.cpp:38-49; Frame::calcDescriptors, frame.h:77-86):
  * cv::ORB::compute.  May DROP keypoints (feature_match.h:15-17): kps/n are in/out.  desc: n*32 bytes.
  * rgb (optional): n*3 bytes, the per-keypoint colour of frame.h:80-85 / basics::getPixelAt

@@ -27,12 +27,18 @@ KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle"
                            ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])   # cv::KeyPoint
 DMATCH_DTYPE = np.dtype([("queryIdx", "<i4"), ("trainIdx", "<i4"), ("imgIdx", "<i4"), ("distance", "<f4")])
 CANDIDATE_DTYPE = np.dtype([("x", "<i2"), ("y", "<i2"), ("level_score", "<i4"), ("harris", "<f4"), ("angle", "<f4")])
+DISTRIBUTE_CANDIDATE_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("level", "<i4"), ("score", "<i4")])
 
 
 class OrbParams(C.Structure):
     _fields_ = [("nfeatures", C.c_int32), ("scale_factor", C.c_float), ("nlevels", C.c_int32),
                 ("fast_threshold", C.c_int32), ("max_keypoints", C.c_int32), ("grid_size", C.c_int32),
                 ("grid_max_per_cell", C.c_int32), ("pyramid_interpolation", C.c_int32)]
+
+
+class OrbDistributeParams(C.Structure):
+    _fields_ = [("ini_threshold", C.c_int32), ("min_threshold", C.c_int32), ("cell_size", C.c_int32),
+                ("edge_threshold", C.c_int32)]
 
 
 class BaProblem(C.Structure):
@@ -199,6 +205,38 @@ class Context:
         out = np.zeros(cap, KEYPOINT_DTYPE)
         n = C.c_int()
         self._chk(self.lib.mvo_calc_keypoints_dev(self.h, C.c_void_p(d_ptr), w, h, stride, ch, _p(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def orb_distribute_configure(self, ini_threshold=20, min_threshold=7, cell_size=30, edge_threshold=19):
+        """Parameters of calc_keypoints_distributed (mvo_orb_distribute_configure)."""
+        p = OrbDistributeParams(int(ini_threshold), int(min_threshold), int(cell_size), int(edge_threshold))
+        self._chk(self.lib.mvo_orb_distribute_configure(self.h, C.byref(p)))
+
+    def calc_keypoints_distributed(self, image, cap=None):
+        """The ORB-SLAM style detector: cell-wise FAST with two thresholds and a quadtree spread per level."""
+        img, w, h, stride, ch = _image_args(image)
+        self._w, self._h = w, h
+        cap = cap or (self.params["max_keypoints"] + 16)
+        out = np.zeros(cap, KEYPOINT_DTYPE)
+        n = C.c_int()
+        self._chk(self.lib.mvo_calc_keypoints_distributed(self.h, _p(img), w, h, stride, ch, _p(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def calc_keypoints_distributed_dev(self, d_ptr, w, h, stride, ch, cap=None):
+        self._w, self._h = w, h
+        cap = cap or (self.params["max_keypoints"] + 16)
+        out = np.zeros(cap, KEYPOINT_DTYPE)
+        n = C.c_int()
+        self._chk(self.lib.mvo_calc_keypoints_distributed_dev(self.h, C.c_void_p(d_ptr), w, h, stride, ch, _p(out), cap,
+                                                              C.byref(n)))
+        return out[:n.value].copy()
+
+    def debug_distribute_candidates(self):
+        """The candidates of the last calc_keypoints_distributed* in their declared order."""
+        n = C.c_int()
+        self._chk(self.lib.mvo_debug_get_distribute_candidates(self.h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), DISTRIBUTE_CANDIDATE_DTYPE)
+        self._chk(self.lib.mvo_debug_get_distribute_candidates(self.h, _p(out), len(out), C.byref(n)))
         return out[:n.value].copy()
 
     def calc_descriptors(self, image, kps, reuse_pyramid=False, want_rgb=False):

@@ -23,6 +23,9 @@
 #define MVO_OPAQUE(x) (void)(x)
 #endif
 
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <atomic>
 #include <string>
@@ -210,6 +213,42 @@ struct mvo_projection_state {  // owned by projection_host.cpp, released through
     int cap_m = 0, cap_t = 0;
 };
 
+// cell-wise FAST + quadtree spread (orb_distribute_kernels.hip / orb_distribute_host.cpp)
+#define DC_MAX_CELL_SIZE 32                        // cell_size W: wCell, hCell <= 2 W - 1 = 63 -> one 64-bit ballot per cell row
+#define DC_MAX_SCORED (2 * DC_MAX_CELL_SIZE - 1)   // scored pixels of a cell per direction
+struct DistCell {  // one cell of k_fast_cells, made once per image geometry (32 bytes)
+    int32_t x0, y0;  // iniX, iniY in level coordinates: the origin of the staged patch
+    int32_t pw, ph;  // staged patch: maxXc - iniX, maxYc - iniY; the scored pixels are [3, pw - 3) x [3, ph - 3) of it
+    int32_t level;
+    int32_t slot;    // first record of the cell's slot in the pinned buffer
+    int32_t cap;     // ceil(sw / 2) * ceil(sh / 2): the most strict 3 x 3 maxima sw x sh scored pixels can hold
+    int32_t pad;
+};
+struct DistRecord {  // a survivor as k_fast_cells emits it and a kept point as k_ic_angle reads it (8 bytes)
+    int16_t x, y;         // level coordinates
+    int32_t level_score;  // level << 16 | FAST score
+};
+struct DistLevel {  // step 1 / step 6 geometry of a level
+    int minX, minY, width, height;
+    int cell0, ncells;  // its cells in the table (cell row, cell column order)
+};
+struct mvo_orb_distribute_state {  // owned by orb_distribute_host.cpp, released through mvo_ctx::dist_release
+    mvo_orb_distribute_params params{20, 7, 30, 19};
+    // what the cell table below was made for
+    bool made = false;
+    mvo_orb_params made_orb{};
+    mvo_orb_distribute_params made_params{};
+    int made_w = 0, made_h = 0;
+    std::vector<DistCell> cells;
+    DistLevel lv[MVO_MAX_LEVELS] = {};
+    size_t n_records = 0;  // sum of the slot capacities
+    int kp_cap = 0;        // most key points a frame can keep (quota + 2 per level, or the initial nodes)
+    DistCell* d_cells = nullptr;
+    signed char* d_disc = nullptr;  // (u, v) of the 749 pixels of the IC-angle disc
+    int disc_n = 0;
+    std::vector<mvo_distribute_candidate> last_cand;  // step 5 of the last call (debug getter)
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -293,6 +332,10 @@ struct mvo_ctx {
     // --- tracking by projection: allocated by the first mvo_map_match_knn2_projection*, released like the undistortion
     mvo_projection_state* proj = nullptr;
     void (*proj_release)(mvo_ctx*) = nullptr;
+    // --- cell-wise FAST + quadtree spread: allocated by the first mvo_orb_distribute_configure /
+    // mvo_calc_keypoints_distributed*, released like the undistortion
+    mvo_orb_distribute_state* dist = nullptr;
+    void (*dist_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -327,6 +370,29 @@ struct ProfScope {
     }
     ~ProfScope() {
         if (c->prof) mvo_prof_end(c);
+    }
+};
+
+// MVO_HOST_TIMING=1: per-stage wall clock of the host half (printed every 200 frames to stderr; development aid)
+struct HostTimes {
+    double acc[8] = {0};
+    long n = 0;
+    std::chrono::steady_clock::time_point t;
+    bool on = std::getenv("MVO_HOST_TIMING") != nullptr;
+    void start() {
+        if (on) t = std::chrono::steady_clock::now();
+    }
+    void lap(int k) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        acc[k] += std::chrono::duration<double, std::micro>(now - t).count();
+        t = now;
+    }
+    void frame(const char* const* names, int cnt) {
+        if (!on || ++n % 200) return;
+        std::fprintf(stderr, "[mvo host us/frame]");
+        for (int k = 0; k < cnt; ++k) std::fprintf(stderr, " %s %.1f", names[k], acc[k] / 200), acc[k] = 0;
+        std::fprintf(stderr, "\n");
     }
 };
 
@@ -390,6 +456,10 @@ int epipolar_launch_knn2(mvo_ctx* ctx, const uint8_t* d_q, const float* d_qxy, i
 int projection_groups(int nt);
 int projection_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, int n_map, const TrackViewArgs& a, const uint8_t* d_t,
                       const double* d_tg, int nt, unsigned long long* d_part, int32_t* d_part_cnt, int32_t* d_arrive, int32_t* out);
+// orb_distribute_kernels.hip
+int dist_launch_cells(mvo_ctx* ctx, const DistCell* d_cells, int n_cells, int thr_min, int thr_ini, int32_t* counts,
+                      DistRecord* records);
+int dist_launch_ic_angle(mvo_ctx* ctx, const signed char* d_disc, int disc_n, const DistRecord* kps, int n, float* angles);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -5,7 +5,6 @@
 // reference's selectUniformKptsByGrid (src/geometry/feature_match.cpp:51-84) is first-come, so the *set* of
 // surviving keypoints depends on libstdc++'s element order; <= 10^4 items, ~0.1 ms.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -13,28 +12,6 @@
 
 #include "mvo_internal.h"
 
-// MVO_HOST_TIMING=1: per-stage wall clock of the host half (printed every 200 frames to stderr; development aid)
-struct HostTimes {
-    double acc[8] = {0};
-    long n = 0;
-    std::chrono::steady_clock::time_point t;
-    bool on = std::getenv("MVO_HOST_TIMING") != nullptr;
-    void start() {
-        if (on) t = std::chrono::steady_clock::now();
-    }
-    void lap(int k) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        acc[k] += std::chrono::duration<double, std::micro>(now - t).count();
-        t = now;
-    }
-    void frame(const char* const* names, int cnt) {
-        if (!on || ++n % 200) return;
-        std::fprintf(stderr, "[mvo host us/frame]");
-        for (int k = 0; k < cnt; ++k) std::fprintf(stderr, " %s %.1f", names[k], acc[k] / 200), acc[k] = 0;
-        std::fprintf(stderr, "\n");
-    }
-};
 static thread_local HostTimes g_ht_detect, g_ht_describe;
 
 namespace {

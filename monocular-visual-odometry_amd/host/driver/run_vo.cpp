@@ -40,6 +40,12 @@
 // records after MORD: PRVP = the 32 f64 of T_prev2 and T_prev as used (T_prev twice without a prev2), PRED = the 16 f64 of
 // the predicted pose, PPOS / PDSC = the map's positions (n x 3 f32) and descriptors (n x 32) as uploaded, in MORD order,
 // MPRJ = the matches handed to PnP before the inlier selection (queryIdx -> index among the points in view).
+// Optional key `orb_distribute_keypoints` (0 / 1, default 0): 1 makes Frame::calcKeyPoints extract the ORB-SLAM way -- FAST cell by
+// cell with two thresholds, a quadtree spread per level (my_slam/geometry/orb_distribute.h; the reference's README.md section 5)
+// -- instead of cv::ORB::detect (feature_match.cpp:22-23).  Its four parameters, optional as well: `orb_distribute_ini_threshold`
+// (default 20), `orb_distribute_min_threshold` (7), `orb_distribute_cell_size` (30), `orb_distribute_edge_threshold` (19).  With
+// the key on, the first frame of the log carries ORBD = the four parameters (int32) after FRAM and every frame ODCN after DESC = int32
+// nlevels, the candidates per level, the key points per level as detected (KPTS holds those calcDescriptors kept).
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -68,6 +74,9 @@
 // ... or without tracking by projection (`tracking_match_by_projection`): likewise
 #pragma weak mvo_predict_pose
 #pragma weak mvo_map_match_features_projection
+// ... or without the cell-wise detector (`orb_distribute_keypoints`): likewise
+#pragma weak mvo_orb_distribute_configure
+#pragma weak mvo_calc_keypoints_distributed
 
 using namespace my_slam;
 
@@ -75,6 +84,7 @@ namespace {
 // record = 4-character tag, int64 byte count, payload; a frame starts with "FRAM"
 struct FrameLog {
     FILE* f = nullptr;
+    bool params_logged = false;  // ORBD goes into the first frame
     ~FrameLog() {
         if (f) fclose(f);
     }
@@ -93,8 +103,25 @@ struct FrameLog {
         static_assert(sizeof(cv::KeyPoint) == 28 && sizeof(cv::DMatch) == 16, "record layouts");
         const int head[2] = {img_id, fr->id_};
         put("FRAM", head, sizeof head);
+        if (geometry::orbDistributeKeypoints() && !params_logged) {
+            const mvo_orb_distribute_params p = geometry::orbDistributeParams();
+            put("ORBD", &p, sizeof p);
+            params_logged = true;
+        }
         vec("KPTS", fr->keypoints_);
         put("DESC", fr->descriptors_.data, (size_t)fr->descriptors_.rows * 32);
+        if (!fr->distribute_candidates_per_level_.empty()) {  // `orb_distribute_keypoints: 1`
+            vector<int> rec(1, (int)fr->distribute_candidates_per_level_.size());
+            rec.insert(rec.end(), fr->distribute_candidates_per_level_.begin(), fr->distribute_candidates_per_level_.end());
+            rec.insert(rec.end(), fr->distribute_keypoints_per_level_.begin(), fr->distribute_keypoints_per_level_.end());
+            vec("ODCN", rec);
+        }
+    }
+    // opens the log of `save_frame_log_to`, if asked for
+    void open() {
+        if (!basics::Config::has("save_frame_log_to")) return;
+        f = fopen(basics::Config::get<string>("save_frame_log_to").c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot open save_frame_log_to");
     }
     void tracked(const vo::MapOnDevice& dev_map, const vo::Frame::Ptr& fr, bool good, bool is_keyframe) {
         vector<int> order;
@@ -245,14 +272,18 @@ int main(int argc, char** argv) {
                 throw std::runtime_error("tracking_match_by_projection: this libmvo_hip.so has no mvo_map_match_features_projection");
             printf("frames are tracked by projection of the map with a predicted pose\n");
         }
+        if (geometry::orbDistributeKeypoints()) {
+            if (!mvo_orb_distribute_configure || !mvo_calc_keypoints_distributed)
+                throw std::runtime_error("orb_distribute_keypoints: this libmvo_hip.so has no mvo_calc_keypoints_distributed");
+            const mvo_orb_distribute_params p = geometry::orbDistributeParams();
+            printf("key points by cell-wise FAST (%d / %d, cells of %d px, edge %d) and a quadtree spread\n", p.ini_threshold,
+                   p.min_threshold, p.cell_size, p.edge_threshold);
+        }
         const int max_num_imgs_to_proc = basics::Config::get<int>("max_num_imgs_to_proc");
         const bool init_from_images = basics::Config::has("init_from_images") && basics::Config::get<int>("init_from_images") != 0;
         if (init_from_images) {
             FrameLog log;
-            if (basics::Config::has("save_frame_log_to")) {
-                log.f = fopen(basics::Config::get<string>("save_frame_log_to").c_str(), "wb");
-                if (!log.f) throw std::runtime_error("cannot open save_frame_log_to");
-            }
+            log.open();
             return runFromImages(image_paths, K, dist, std::min(max_num_imgs_to_proc, (int)image_paths.size()), log);
         }
         const vector<cv::Mat> truth = vo::readPoseFromFile(basics::Config::get<string>(sec + "true_traj_filename"));
@@ -261,10 +292,7 @@ int main(int argc, char** argv) {
         if (k0 < 0 || k1 <= k0 || k1 >= (int)truth.size()) throw std::runtime_error("init_keyframe_0/1 outside the ground-truth trajectory");
 
         FrameLog log;
-        if (basics::Config::has("save_frame_log_to")) {
-            log.f = fopen(basics::Config::get<string>("save_frame_log_to").c_str(), "wb");
-            if (!log.f) throw std::runtime_error("cannot open save_frame_log_to");
-        }
+        log.open();
         vo::TrackingState st;
         vector<cv::Mat> cam_pose_history;
         int n_tracked = 0, n_lost = 0, n_keyframes = 0;

@@ -4,6 +4,7 @@
 #define MY_SLAM_FRAME_H
 #include "my_slam/common_include.h"
 #include "my_slam/geometry/feature_match.h"
+#include "my_slam/geometry/orb_distribute.h"
 
 namespace my_slam {
 namespace vo {
@@ -54,6 +55,10 @@ public:
     vector<float> projection_map_pos_;
     vector<unsigned char> projection_map_desc_;
     vector<cv::DMatch> projection_matches_;
+    // (not in the reference) `orb_distribute_keypoints: 1`: per pyramid level, the candidates of calcKeyPoints and the key
+    // points it kept (before calcDescriptors drops those near the image border); empty otherwise
+    vector<int> distribute_candidates_per_level_;
+    vector<int> distribute_keypoints_per_level_;
 
     // -- Current pose (cam -> world, see vo.cpp:31,89)
     cv::Mat T_w_c_;
@@ -75,7 +80,10 @@ public:
         matches_with_map_.clear();
     }
     void calcKeyPoints() {
-        geometry::calcKeyPoints(rgb_img_, keypoints_);
+        if (geometry::orbDistributeKeypoints())  // the ORB-SLAM way (my_slam/geometry/orb_distribute.h)
+            geometry::calcKeyPointsDistributed(rgb_img_, keypoints_, &distribute_candidates_per_level_, &distribute_keypoints_per_level_);
+        else
+            geometry::calcKeyPoints(rgb_img_, keypoints_);
         geometry::detail::pyramid_token() = (long long)id_ + 1;  // the ctx now caches THIS frame's pyramid
     }
     void calcDescriptors() {
