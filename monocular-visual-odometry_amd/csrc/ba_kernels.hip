@@ -393,6 +393,14 @@ __device__ __forceinline__ void asm_waitcnt_vm0() {
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
 #endif
 }
+// The same value behind a point the compiler cannot see through: what is derived from it afterwards is computed afterwards, not
+// once ahead of the LM loop and then carried -- in scratch memory, for lack of registers -- through all of it (BA_PHASE_HEAD).
+__device__ __forceinline__ int ba_fresh_i(int v) {
+#ifndef MVO_KERNEL_SIM
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
 // the XCD this workgroup runs on (placement is used for speed only, never for results)
 __device__ __forceinline__ unsigned ba_xcc_id() {
 #ifndef MVO_KERNEL_SIM
@@ -771,7 +779,17 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
     __shared__ long long sStamp[PROF ? 32 : 1];  // (parked in LDS: a store to host memory in front of a barrier would be timed)
     if (threadIdx.x == 0) sFlag[1] = sFlag[2] = sFlag[3] = sFlag[4] = 0;  // [1] NaN on the diagonal, [2] exchange timed out, [3] equal diagonal entries, [4] ranks changed
     if (threadIdx.x < 6 * BA_MAX_POSES) sRank[threadIdx.x] = -1;  // (no order replayed yet)
-    const int tid = threadIdx.x, lane = tid & 63;
+    // (not const: every phase of the LM loop takes them afresh, BA_PHASE_HEAD.  The per-thread LDS addresses and predicates of a phase
+    // are one or two integer instructions away from the thread index; left to the compiler they are all formed once, ahead of the
+    // loop -- they are loop invariants -- and, with no registers to carry them through it, re-read from scratch memory at the head of
+    // the phase that uses them, right behind a barrier: 36 re-reads per trial and 96 spilled registers in k_ba_service<32,2>, 3 and
+    // 22 with the phase heads; the launch-path flavours of the 5-pose class spill none.  profiles/r07_ab_runs.txt)
+    int tid = threadIdx.x, lane = tid & 63;
+#define BA_PHASE_HEAD()            \
+    do {                           \
+        tid = ba_fresh_i(tid);     \
+        lane = tid & 63;           \
+    } while (0)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = B.n, G = B.G, nfree = B.nfree, urows = B.ldu, ldu = B.ldu + 1, nlow = B.nlow, npk = B.npk;
     const int pt_lo = B.wg_pt_start[g], Lg = B.wg_pt_start[g + 1] - pt_lo;
@@ -1022,6 +1040,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
         // ================= LIN: whitened Jacobians of the own edges (EdgeProjectXYZ2UV::linearizeOplus), kept in registers;
         // X~ and e~ also go to the staging area for the landmark blocks
         PH_BEGIN();
+        BA_PHASE_HEAD();
         double ee0[2] = {0, 0};  // e~ of the register edge (needed again when the chain rows are staged)
 // rows of edge `el` (pose p, slot sl) into r, its whitened error into ee; X~ and e~ also into the staging area
 #define BA_LINEARIZE(el, r, p, sl, ee)                                                                              \
@@ -1077,6 +1096,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
         // in the order of the landmark-grouped edge list, one slice of the range's landmarks per pass (B.npt passes: the area
         // need not hold all edges at once), and read back sequentially by the landmark's thread.
         double maxdiag = 0;
+        BA_PHASE_HEAD();
         if (!B.fix_points) {
             for (int h = 0; h < B.npt; ++h) {
                 const int l_lo = (int)((long long)Lg * h / B.npt), l_hi = (int)((long long)Lg * (h + 1) / B.npt);
@@ -1124,6 +1144,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
         const bool hp_deferred = do_schur && G > 1 && it > 0;
         const bool hp_local = hp_deferred || G == 1;  // results stay in this workgroup's hpl
         if (!hp_deferred) ++tagH;
+        BA_PHASE_HEAD();
         {
             // The rows are staged in `hp_npass` passes (tables made once per solve, above): pass q holds, for EVERY pose, the q-th
             // slice of its rows, all slices of a pass packed back to back.  Every chain therefore runs in every pass -- side by
@@ -1245,6 +1266,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
         PH_END(1);
         // ---- exchange: pose-block partials + the landmark max diagonal, summed in workgroup order; the partials are
         // staged `hrows` workgroups at a time (the staging area is bounded for windows with many workgroups)
+        BA_PHASE_HEAD();
         if (!hp_deferred) {
             const double m = block_max(maxdiag, sScr);
             const int nhp = B.nhp, hrows = min(G, max(1, (int)(B.uarea / nhp)));
@@ -1294,6 +1316,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
         bool hp_pending = hp_deferred;
         do {
             STAMP(0);
+            BA_PHASE_HEAD();
             // ============= T1: (H_ll + lambda I)^-1 = C C^T and C^T b_l of the own landmarks
             int ist = nlow;  // where the summed stale-scale entry ends up in Rl
             if (!B.fix_points) {
@@ -1324,6 +1347,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             // ============= T2: partial Schur system of the own landmarks.  U_l = [W_l C_l ; (C_l^T b_l)^T ; 0] (one column per
             // landmark coordinate) is built one CHUNK of columns at a time in the U area and consumed by the MFMA chains of that
             // chunk: one chain per (tile pair, column piece); the pieces of a pair are added in piece order.
+            BA_PHASE_HEAD();
             if (do_schur) {
                 ++tagA;
                 double* split_stage = W.SL;  // (free until the assemble step) npair x (npar - 1) x 256
@@ -1471,6 +1495,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
                 PH_END(4);
                 if (G > 1) {
                     __syncthreads();
+                    BA_PHASE_HEAD();
                     STAMP(6);
                     // stage 1: this workgroup reduces its SLICE of the packed entries over the partials of its group (the
                     // workgroups w = g mod K; K = 1: all of them), in workgroup order, and republishes the slice.  A window
@@ -1511,6 +1536,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
                         gstore_d(xR + 2 * ((size_t)gk * npk + sl0 + el), tag0 + tagA, sum, same_l2);
                     }
                     STAMP(9);
+                    BA_PHASE_HEAD();
                     // stage 2: everybody reads the summed entries (K > 1: the K group sums, added in group order)
                     if (K == 1) {
                         if (!gather_tagged(xR, nlowx, nlowx, 0, tag0 + tagA, W.Rl, PROF ? &ph[PROF ? 13 : 0] : nullptr)) sFlag[2] = 1;
@@ -1550,6 +1576,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             PH_END(5);
             // ============= T3: every workgroup assembles S = H_pp + lambda I - G, g = b_p - G[:, n] -- rows and columns in the
             // pivot order Eigen::LDLT would choose for it (sPerm, from |diag S|) -- and solves it
+            BA_PHASE_HEAD();
             int pw = 0;  // the trial's pivot order = sPermAll[pw]: by ranks, or the replayed one when entries tie (an index, not a
                          // pointer: a pointer selected between two LDS arrays is generic to the compiler)
 #define perm sPermAll[pw]
@@ -1617,6 +1644,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
                 }
                 STAMP(27);
             }
+            BA_PHASE_HEAD();
             if (NR != 0) {
                 // register solvers: the system embedded into NR rows (identity rows behind n, the rhs as row NR - 1)
                 constexpr int NRR = NR ? (NR < 0 ? -NR : NR) : 32, RR = NRR - 1, PP = NRR + 1;
@@ -1663,6 +1691,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             __syncthreads();
             STAMP(12);
             PH_END(6);
+            BA_PHASE_HEAD();
             if (wave == BA_WAVES - 1) {
                 // what g2o's LM would make of THIS trial if the solve below fails: it applies the solver's x all the same -- still
                 // the previous solution (sDx / dxl) --, sets tempChi = DBL_MAX and divides by computeScale() of that stale x.  Formed
@@ -1699,6 +1728,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             }
             __syncthreads();
 #undef perm
+            BA_PHASE_HEAD();
             const int ok2 = sFlag[0];
             if (tid == 0) sFlag[1] = sFlag[3] = sFlag[4] = 0;  // (re-armed for the next trial's pivot order: read before the solve, written again many barriers later)
             if (ok2 && tid < 6 * B.F) {
@@ -1708,6 +1738,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             __syncthreads();
             STAMP(13);
             PH_END(7);
+            BA_PHASE_HEAD();
             const double lambda_used = lambda;
             ++trials;
             double stale_rho = 0;
@@ -1767,6 +1798,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             STAMP(14);
             __syncthreads();
             STAMP(15);
+            BA_PHASE_HEAD();
             // the poses (last wave: push + oplus, a long serial chain) and the landmarks (first waves) update side by side
             if (tid >= BA_THREADS - 64 && tid - (BA_THREADS - 64) < B.F) {
                 const int p = tid - (BA_THREADS - 64);
@@ -1824,10 +1856,12 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
             __syncthreads();
             STAMP(18);
             PH_END(8);
+            BA_PHASE_HEAD();
             // ============= T6/T7: robust chi2 at the trial state, identical accept / reject decision everywhere
             double tempChi = robust_chi2_local(B, W, Eg, sR, sT, sScr);
             STAMP(19);
             PH_END(9);
+            BA_PHASE_HEAD();
             if (G > 1) {
                 ++tagB;
                 u64* slot = B.xC + (size_t)(tagB & 1) * G * 4;
@@ -1863,6 +1897,7 @@ __device__ __forceinline__ void ba_window(const BaDev* desc, const BaRun batch, 
                 }
             }
             STAMP(22);
+            BA_PHASE_HEAD();
             scale += 1e-3;
             const double chi_at_state = tempChi;  // (what the next iteration's computeActiveErrors sees)
             if (!ok2) tempChi = 1.7976931348623157e308;
