@@ -423,6 +423,31 @@ int mvo_map_size(mvo_ctx* ctx, mvo_map* map, int* n);
  * mvo_invert_pose, each product summed k = 0..3 in order, no re-orthonormalisation).  T_w_c_prev2 NULL: T_pred = T_prev.
  * MVO_ERR_INVALID for a singular T_prev2. */
 int mvo_predict_pose(const double* T_w_c_prev2 /* or NULL */, const double* T_w_c_prev, double* T_w_c_pred);
+/* ---- map points refreshed from their observations --------------------------------------------- */
+/* The reference gives a map point the descriptor and the viewing direction of the ONE frame that created it
+ * (pushCurrPointsToMap_, vo.cpp:528-576) and never writes them again; ORB-SLAM, whose matching the calls above follow, keeps a
+ * map point as the summary of all its observations.  Declared operation by operation in DESIGN.md section 17:
+ *   D[k][j]   256-bit Hamming distance of observations k and j of the point, D[k][k] = 0 included
+ *   med[k]    the element at index (m - 1) / 2 (integer division) of row k sorted ascending (ORB-SLAM's vDists[0.5*(N-1)])
+ *   choice    the k with the smallest med[k], the lowest k on a tie
+ *   normal    p = (double) of the resident f32 position; per observation d_r = p_r - c_r, s = d_x d_x; s = s + d_y d_y;
+ *             s = s + d_z d_z; u_r = d_r / sqrt(s); S_r = sum of u_r from 0.0 in observation order; t = S_x S_x; t = t + S_y S_y;
+ *             t = t + S_z S_z; norm_r = S_r / sqrt(t).  A point at a camera centre gives NaN, written as it comes.
+ * Observations of point i are rows obs_start[i] .. obs_start[i + 1] - 1 of obs_desc / obs_cam (the camera centres, world
+ * coordinates); n = mvo_map_size.  A point without observations: choice -1, descriptor unchanged, norm_out (0, 0, 0).
+ * MVO_ERR_INVALID: a null map, a null pointer with a positive count, obs_start[0] != 0, obs_start[n] != n_obs, a decreasing
+ * obs_start, a non-finite obs_cam.  MVO_ERR_CAPACITY: a point with more than 64 observations; nothing is written.  An empty
+ * map succeeds without a launch; n_obs == 0 succeeds, every choice -1. */
+/* ORB-SLAM MapPoint::ComputeDistinctiveDescriptors + MapPoint::UpdateNormalAndDepth, in place of vo.cpp:528-576's single copy
+ * (MapPoint::descriptor_, norm_; norm_ is read by getViewAngle_, vo.cpp:578-584).  One launch (k_map_refresh): the resident
+ * descriptor of every observed point becomes its chosen observation's 32 bytes, in HBM.  desc_out receives the resident
+ * descriptors after the call. */
+int mvo_map_refresh(mvo_ctx* ctx, mvo_map* map, const uint8_t* obs_desc /* n_obs x 32 */, const double* obs_cam /* n_obs x 3 */,
+                    const int32_t* obs_start /* n + 1, n = mvo_map_size */, int n_obs, int32_t* choice /* n */,
+                    uint8_t* desc_out /* n x 32, may be NULL */, double* norm_out /* n x 3 */);
+/* include/my_slam/vo/map.h:19 (map_points_: MapPoint::pos_, descriptor_ of the resident copy).  The resident arrays, for
+ * tests: pos n x 3 f32, desc n x 32 (either may be NULL); *n = mvo_map_size; MVO_ERR_CAPACITY (with *n set) if cap < *n. */
+int mvo_debug_get_map(mvo_ctx* ctx, mvo_map* map, float* pos, uint8_t* desc, int cap, int* n);
 /* ---- keyframe insertion: epipolar inlier filter, triangulation, culling ---- */
 /* geometry::helperTriangulatePoints (src/geometry/motion_estimation.cpp:214-247, called at
  * vo_addFrame.cpp:114-116): pixel2CamNormPlane on the matched pixels of the previous / current keyframe

@@ -465,6 +465,34 @@ class Context:
                                                              _p(px), _p(in_view), _p(out), cap, C.byref(cnt)))
         return out[:cnt.value].copy(), px, in_view.astype(bool)
 
+    def map_refresh(self, m, obs_desc, obs_cam, obs_start):
+        """mvo_map_refresh: every map point takes the medoid of its observations' descriptors (in HBM) and the mean of their
+        unit viewing directions -> (choice n int32, -1: no observation; desc n x 32, the resident descriptors after the call;
+        norm n x 3 f64).  Observations of point i: rows obs_start[i] .. obs_start[i + 1] - 1."""
+        if not hasattr(self.lib, "mvo_map_refresh"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_map_refresh")
+        obs_desc = np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32)
+        obs_cam = np.ascontiguousarray(obs_cam, np.float64).reshape(-1, 3)
+        obs_start = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+        if len(obs_desc) != len(obs_cam):
+            raise ValueError("one camera centre per observation descriptor")
+        n = self._map_size(m)
+        if len(obs_start) != n + 1:
+            raise ValueError("obs_start needs one entry per map point and one more")
+        choice, desc, norm = np.zeros(n, np.int32), np.zeros((n, 32), np.uint8), np.zeros((n, 3), np.float64)
+        self._chk(self.lib.mvo_map_refresh(self.h, m, _p(obs_desc), _p(obs_cam), _p(obs_start), len(obs_desc), _p(choice), _p(desc),
+                                           _p(norm)))
+        return choice, desc, norm
+
+    def map_debug_get(self, m):
+        """mvo_debug_get_map: the resident arrays -> (pos n x 3 f32, desc n x 32)."""
+        n = self._map_size(m)
+        pos, desc = np.zeros((n, 3), np.float32), np.zeros((n, 32), np.uint8)
+        cnt = C.c_int()
+        self._chk(self.lib.mvo_debug_get_map(self.h, m, _p(pos), _p(desc), n, C.byref(cnt)))
+        assert cnt.value == n
+        return pos, desc
+
     # ---- bundle adjustment
     def _ba_problem(self, poses, points, edge_pose, edge_point, edge_uv, focal, cx, cy, info, huber_delta,
                     fix_points, pose_fixed, max_iterations):

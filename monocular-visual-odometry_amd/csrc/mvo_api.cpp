@@ -178,6 +178,7 @@ void mvo_destroy(mvo_ctx* ctx) {
     if (ctx->epi_release) ctx->epi_release(ctx);
     if (ctx->proj_release) ctx->proj_release(ctx);
     if (ctx->dist_release) ctx->dist_release(ctx);
+    if (ctx->refresh_release) ctx->refresh_release(ctx);
     ba_pool_release(ctx);
     void* dev[] = {ctx->d_img, ctx->d_raw,  ctx->d_blur, ctx->d_tabs, ctx->d_pyr_regs,
                    ctx->d_kp,   ctx->d_desc_buf, ctx->d_mq,    ctx->d_mt,   ctx->d_mqxy,      ctx->d_mtxy,

@@ -249,6 +249,13 @@ struct mvo_orb_distribute_state {  // owned by orb_distribute_host.cpp, released
     std::vector<mvo_distribute_candidate> last_cand;  // step 5 of the last call (debug getter)
 };
 
+// map points refreshed from their observations (map_refresh_kernels.hip / map_refresh_host.cpp)
+#define MR_MAX_OBS 64  // observations per map point: one lane each
+struct mvo_refresh_state {  // owned by map_refresh_host.cpp, released through mvo_ctx::refresh_release
+    uint8_t* d_in = nullptr;  // one upload per call: the camera centres, the descriptors, the n + 1 starts
+    size_t cap = 0;           // bytes
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -336,6 +343,9 @@ struct mvo_ctx {
     // mvo_calc_keypoints_distributed*, released like the undistortion
     mvo_orb_distribute_state* dist = nullptr;
     void (*dist_release)(mvo_ctx*) = nullptr;
+    // --- map points refreshed from their observations: allocated by the first mvo_map_refresh, released like the undistortion
+    mvo_refresh_state* refresh = nullptr;
+    void (*refresh_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -460,6 +470,9 @@ int projection_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, i
 int dist_launch_cells(mvo_ctx* ctx, const DistCell* d_cells, int n_cells, int thr_min, int thr_ini, int32_t* counts,
                       DistRecord* records);
 int dist_launch_ic_angle(mvo_ctx* ctx, const signed char* d_disc, int disc_n, const DistRecord* kps, int n, float* angles);
+// map_refresh_kernels.hip
+int map_refresh_launch(mvo_ctx* ctx, const float* d_pos, uint8_t* d_desc, int n, const uint8_t* d_obs_desc, const double* d_obs_cam,
+                       const int32_t* d_obs_start, int32_t* out_choice, uint8_t* out_desc, double* out_norm);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

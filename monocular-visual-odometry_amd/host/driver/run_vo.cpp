@@ -46,6 +46,14 @@
 // (default 20), `orb_distribute_min_threshold` (7), `orb_distribute_cell_size` (30), `orb_distribute_edge_threshold` (19).  With
 // the key on, the first frame of the log carries ORBD = the four parameters (int32) after FRAM and every frame ODCN after DESC = int32
 // nlevels, the candidates per level, the key points per level as detected (KPTS holds those calcDescriptors kept).
+// Optional key `map_point_refresh` (0 / 1, default 0): 1 makes every keyframe insertion while tracking end, right after the culling
+// (optimizeMap_), with a refresh of the map points from their observations in the last 20 frames (my_slam/vo/map_refresh.h;
+// ORB-SLAM's MapPoint::ComputeDistinctiveDescriptors and UpdateNormalAndDepth): the descriptor becomes the observation with the
+// least median Hamming distance to the others, the normal the mean unit viewing direction; the reference keeps both from the frame
+// that created the point (vo.cpp:528-576).  With the key on, a keyframe's part of the frame log carries six more records after
+// MPOS, in the order of MIDS: ROBS = the n + 1 observation starts (int32), RDSC / RCAM = the observations' descriptors (n_obs x
+// 32) and camera centres (n_obs x 3 f64), RPOS = the positions as resident (n x 3 f32), RCHO = the chosen observation per point
+// (int32, -1: none), RNRM = the normals (n x 3 f64); and MORD of such a frame stays what its own tracking step saw.
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -74,6 +82,8 @@
 // ... or without tracking by projection (`tracking_match_by_projection`): likewise
 #pragma weak mvo_predict_pose
 #pragma weak mvo_map_match_features_projection
+// ... or without the map-point refresh (`map_point_refresh`): likewise
+#pragma weak mvo_map_refresh
 // ... or without the cell-wise detector (`orb_distribute_keypoints`): likewise
 #pragma weak mvo_orb_distribute_configure
 #pragma weak mvo_calc_keypoints_distributed
@@ -126,6 +136,7 @@ struct FrameLog {
     void tracked(const vo::MapOnDevice& dev_map, const vo::Frame::Ptr& fr, bool good, bool is_keyframe) {
         vector<int> order;
         for (const vo::MapPoint::Ptr& p : dev_map.order()) order.push_back(p->id_);
+        if (fr->refreshed_) order = fr->refresh_order_before_;  // `map_point_refresh: 1`: the refresh has re-read the map since
         vec("MORD", order);  // iteration order of Map::map_points_ when the frame looked at the map
         if (!fr->projection_pred_T_.empty()) {  // `tracking_match_by_projection: 1`: what the matcher saw
             vec("PRVP", fr->projection_prev_T_);
@@ -154,6 +165,18 @@ struct FrameLog {
         }
         triangulated(fr);
         mapAfter(map);
+        if (fr->refreshed_) {  // `map_point_refresh: 1`: what the refresh saw and gave
+            vec("ROBS", fr->refresh_obs_start_);
+            vec("RDSC", fr->refresh_obs_desc_);
+            vec("RCAM", fr->refresh_obs_cam_);
+            vec("RPOS", fr->refresh_pos_);
+            vec("RCHO", fr->refresh_choice_);
+            vec("RNRM", fr->refresh_norm_);
+            int n_seen = 0, n_moved = 0;
+            for (int c : fr->refresh_choice_) n_seen += c >= 0 ? 1 : 0, n_moved += c > 0 ? 1 : 0;
+            printf("frame %d: %d map points refreshed from %d observations (%d observed, %d took another descriptor than their first)\n",
+                   fr->id_, (int)fr->refresh_choice_.size(), fr->refresh_obs_start_.back(), n_seen, n_moved);  // (with or without a log file)
+        }
     }
     void initialization(const vo::Map::Ptr& map, const vo::Frame::Ptr& fr, const vo::InitReport& rep, bool initialized) {
         vec("MREF", fr->matches_with_ref_);  // the matches with the first keyframe
@@ -271,6 +294,10 @@ int main(int argc, char** argv) {
             if (!mvo_predict_pose || !mvo_map_match_features_projection)
                 throw std::runtime_error("tracking_match_by_projection: this libmvo_hip.so has no mvo_map_match_features_projection");
             printf("frames are tracked by projection of the map with a predicted pose\n");
+        }
+        if (vo::mapPointRefresh()) {
+            if (!mvo_map_refresh) throw std::runtime_error("map_point_refresh: this libmvo_hip.so has no mvo_map_refresh");
+            printf("map points take descriptor and normal from their observations at every keyframe\n");
         }
         if (geometry::orbDistributeKeypoints()) {
             if (!mvo_orb_distribute_configure || !mvo_calc_keypoints_distributed)

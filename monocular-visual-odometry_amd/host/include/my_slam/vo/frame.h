@@ -55,6 +55,19 @@ public:
     vector<float> projection_map_pos_;
     vector<unsigned char> projection_map_desc_;
     vector<cv::DMatch> projection_matches_;
+    // (not in the reference) `map_point_refresh: 1`, on the keyframe after whose insertion the map points were refreshed
+    // (my_slam/vo/map_refresh.h): the ids of MapOnDevice::order() as the frame's own tracking step saw it (the refresh re-reads
+    // the map), then in the order of the refreshed map: the observation starts (n + 1), the observations' descriptors
+    // (n_obs x 32) and camera centres (n_obs x 3), the positions as resident (n x 3), the chosen observation per point and the
+    // normals (n x 3); empty otherwise
+    vector<int> refresh_order_before_;
+    vector<int> refresh_obs_start_;
+    vector<unsigned char> refresh_obs_desc_;
+    vector<double> refresh_obs_cam_;
+    vector<float> refresh_pos_;
+    vector<int> refresh_choice_;
+    vector<double> refresh_norm_;
+    bool refreshed_ = false;
     // (not in the reference) `orb_distribute_keypoints: 1`: per pyramid level, the candidates of calcKeyPoints and the key
     // points it kept (before calcDescriptors drops those near the image border); empty otherwise
     vector<int> distribute_candidates_per_level_;
@@ -78,6 +91,13 @@ public:
         inliers_matches_with_ref_.clear();
         inliers_matches_for_3d_.clear();
         matches_with_map_.clear();
+        refresh_order_before_.clear();  // (logged by now; refreshed_ stays)
+        refresh_obs_start_.clear();
+        refresh_obs_desc_.clear();
+        refresh_obs_cam_.clear();
+        refresh_pos_.clear();
+        refresh_choice_.clear();
+        refresh_norm_.clear();
     }
     void calcKeyPoints() {
         if (geometry::orbDistributeKeypoints())  // the ORB-SLAM way (my_slam/geometry/orb_distribute.h)

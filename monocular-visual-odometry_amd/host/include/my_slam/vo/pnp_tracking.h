@@ -116,6 +116,8 @@ public:
     const unsigned char* descriptor(int i) const { return &desc_[32 * (size_t)i]; }
     const vector<float>& positions() const { return pos_; }            // n x 3, as uploaded by the last sync()
     const vector<unsigned char>& descriptors() const { return desc_; }  // n x 32
+    // the map-point refresh (my_slam/vo/map_refresh.h) has rewritten row i in HBM: the host copy follows
+    void setDescriptor(int i, const unsigned char* d) { std::memcpy(&desc_[32 * (size_t)i], d, 32); }
 
 private:
     mvo_map* map_ = nullptr;

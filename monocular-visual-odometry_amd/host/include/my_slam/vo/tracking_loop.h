@@ -29,6 +29,13 @@ struct TrackingState {  // the members of VisualOdometry the tracking branch tou
     }
 };
 
+// my_slam/vo/map_refresh.h (included at the end of this header): the refresh of `map_point_refresh: 1`
+inline void refreshMapPoints(TrackingState& st, const Frame::Ptr& curr = nullptr);
+inline bool mapPointRefresh() {  // the optional key, latched on first use
+    static const bool on = basics::Config::has("map_point_refresh") && basics::Config::get<int>("map_point_refresh") != 0;
+    return on;
+}
+
 inline cv::Point3f preTranslatePoint3f(const cv::Point3f& p, const cv::Mat& T) {  // opencv_funcs.cpp:67-78
     const double q[4] = {p.x, p.y, p.z, 1};
     double res[3] = {0, 0, 0};
@@ -142,6 +149,7 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
             triangulateWithReferenceKeyframe(curr, st.ref_, K);
             pushCurrPointsToMap(st, curr);
             optimizeMap(st, curr, K);
+            if (mapPointRefresh()) refreshMapPoints(st, curr);  // descriptor and normal from all observations in the window
             st.map_->insertKeyFrame(curr);  // addKeyFrame_
             st.ref_ = curr;
             if (is_keyframe) *is_keyframe = true;
@@ -154,4 +162,6 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
 
 }  // namespace vo
 }  // namespace my_slam
+
+#include "my_slam/vo/map_refresh.h"
 #endif
