@@ -9,18 +9,17 @@
 #include <cstring>
 #include <vector>
 
-#include "mvo_internal.h"
+#include "guided_match_host.h"
 
 namespace {
-
-const int kMaxTrains = 65535;  // the train index lives in the low 16 bits of a key
 
 void epipolar_release(mvo_ctx* ctx) {
     mvo_epipolar_state* e = ctx->epi;
     if (!e) return;
-    void* dev[] = {e->d_q, e->d_qxy, e->d_part, e->d_out, e->d_t, e->d_txy, e->d_tol2};
+    void* dev[] = {e->d_q, e->d_qxy, e->d_t, e->d_txy, e->d_tol2};
     for (void* p : dev)
         if (p) mvo_free_on_current_device(p);
+    e->scratch.release();
     delete e;
     ctx->epi = nullptr;
 }
@@ -32,23 +31,17 @@ int ensure_bufs(mvo_ctx* ctx, int nq, int nt) {
     }
     mvo_epipolar_state* e = ctx->epi;
     if (nq > e->cap_q) {
-        void* old[] = {e->d_q, e->d_qxy, e->d_part, e->d_out};
+        void* old[] = {e->d_q, e->d_qxy};
         for (void* p : old)
             if (p) mvo_free_on_current_device(p);
-        e->d_q = nullptr, e->d_qxy = nullptr, e->d_part = nullptr, e->d_out = nullptr;
+        e->d_q = nullptr, e->d_qxy = nullptr;
         e->cap_q = 0;
         const size_t cap = (size_t)std::max(4096, nq + nq / 2);
         MVO_HIP(hipMalloc((void**)&e->d_q, cap * 32));
         MVO_HIP(hipMalloc((void**)&e->d_qxy, cap * 8));
-        MVO_HIP(hipMalloc((void**)&e->d_out, cap * 20));
-        // partial key pairs, partial counts, one arrival counter per group of 64 queries (self re-arming, zeroed once)
-        const size_t keys = EK_MAX_GROUPS * cap * 8, cnts = EK_MAX_GROUPS * cap * 4, ctr = (cap / 64 + 2) * 4;
-        MVO_HIP(hipMalloc((void**)&e->d_part, keys + cnts + ctr));
-        e->d_part_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys);
-        e->d_arrive = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys + cnts);
-        MVO_HIP(hipMemsetAsync(e->d_arrive, 0, ctr, ctx->stream));
         e->cap_q = (int)cap;
     }
+    if (int r = e->scratch.ensure(ctx, nq)) return r;  // (grows when cap_q does: the same rule)
     if (nt > e->cap_t) {
         void* old[] = {e->d_t, e->d_txy, e->d_tol2};
         for (void* p : old)
@@ -74,11 +67,7 @@ int check_and_trivial(mvo_ctx* ctx, const void* q, const float* qxy, int nq, con
     for (int k = 0; k < 9; ++k)
         if (!std::isfinite(F[k])) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: F is not finite", hipSuccess);
     if (!(max_line_px >= 0)) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: max_line_px negative or NaN", hipSuccess);
-    if (nt > kMaxTrains) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_match_knn2_epipolar: more than 65535 train descriptors", hipSuccess);
-    if (t_scale)
-        for (int j = 0; j < nt; ++j)
-            if (!std::isfinite(t_scale[j]) || t_scale[j] < 0)
-                return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_match_knn2_epipolar: t_scale entry negative or not finite", hipSuccess);
+    if (int r = guided_check_trains(ctx, "mvo_match_knn2_epipolar", t_scale, nt)) return r;
     if (nq == 0 || nt == 0) {
         for (int i = 0; i < nq; ++i) {
             idx[2 * i] = idx[2 * i + 1] = -1;
@@ -95,10 +84,7 @@ int run(mvo_ctx* ctx, const uint8_t* d_q, const float* qxy, int nq, const uint8_
         int nt, const double* F, double max_line_px, int32_t* idx, int32_t* dist, int32_t* n_candidates) {
     mvo_epipolar_state* e = ctx->epi;
     std::vector<double> tol2(nt);
-    for (int j = 0; j < nt; ++j) {
-        const double tl = max_line_px * (t_scale ? (double)t_scale[j] : 1.0);
-        tol2[j] = tl * tl;
-    }
+    for (int j = 0; j < nt; ++j) tol2[j] = guided_tol2(max_line_px, t_scale, j);
     EpipolarArgs a;
     std::memcpy(a.f, F, sizeof a.f);
     // the kernel writes the nq x (idx[2], dist[2]) block and the counts straight into the pinned staging buffer
@@ -108,7 +94,7 @@ int run(mvo_ctx* ctx, const uint8_t* d_q, const float* qxy, int nq, const uint8_
     MVO_HIP(hipMemcpyAsync(e->d_txy, txy, (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
     MVO_HIP(hipMemcpyAsync(e->d_tol2, tol2.data(), (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
     ExtractGate gate(ctx);
-    if ((r = epipolar_launch_knn2(ctx, d_q, e->d_qxy, nq, d_t, e->d_txy, e->d_tol2, nt, a, e->d_part, e->d_part_cnt, e->d_arrive,
+    if ((r = epipolar_launch_knn2(ctx, d_q, e->d_qxy, nq, d_t, e->d_txy, e->d_tol2, nt, a, e->scratch.partials(),
                                   reinterpret_cast<int32_t*>(ctx->h_pin))))
         return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));  // (tol2 is pageable: its copy has left the vector by now either way)
@@ -162,22 +148,7 @@ int mvo_match_features_epipolar(mvo_ctx* ctx, const uint8_t* d1, const float* xy
     std::vector<int32_t> idx(2 * (size_t)n1 + 2), dist(2 * (size_t)n1 + 2);
     int r = mvo_match_knn2_epipolar(ctx, d1, xy1, n1, d2, xy2, scale2, n2, F, max_line_px, idx.data(), dist.data(), nullptr);
     if (r) return r;
-    // per train the claiming query with the smallest (distance, queryIdx); queries arrive in ascending order
-    std::vector<int32_t> owner(n2 > 0 ? n2 : 1, -1);
-    for (int i = 0; i < n1; ++i) {
-        const int j = idx[2 * i], d0 = dist[2 * i];
-        if (j < 0 || d0 > max_hamming) continue;
-        if (idx[2 * i + 1] >= 0 && !((double)d0 < lowe_ratio * (double)dist[2 * i + 1])) continue;
-        if (owner[j] < 0 || d0 < dist[2 * owner[j]]) owner[j] = i;
-    }
-    int cnt = 0;
-    for (int j = 0; j < n2; ++j) cnt += owner[j] >= 0 ? 1 : 0;
-    *n = cnt;
-    if (cnt > cap || (cnt && !out)) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "match buffer too small", hipSuccess);
-    int k = 0;
-    for (int j = 0; j < n2; ++j)
-        if (owner[j] >= 0) out[k++] = {owner[j], j, 0, (float)dist[2 * owner[j]]};
-    return MVO_OK;
+    return guided_filter_matches(ctx, idx.data(), dist.data(), n1, n2, lowe_ratio, max_hamming, out, cap, n);
 }
 
 // README.md:212 ("based on the estimated camera motion"): the fundamental matrix of the two estimated poses

@@ -12,7 +12,7 @@
 // (distance, index) pairs, which reproduces cv::batchDistance's tie rule exactly (equal distances keep the lower train
 // index).  k_radius_l1 keeps the single-kernel form (16 waves x 64 queries, LDS merge).  Everything is integer: results
 // are bit-exact.  The whole working set (<= 2 x 128 KB) is L2-resident: no HBM bound.
-#include "mvo_internal.h"
+#include "guided_knn2.h"  // knn2_insert, knn2_fold: the top-2 network on keys
 
 #include <climits>
 #include <cstdlib>
@@ -154,10 +154,6 @@ __device__ __forceinline__ uint32_t mm_spread(uint32_t nib) {  // 4 bits -> 4 by
     const uint32_t x = (nib | (nib << 7) | (nib << 14) | (nib << 21)) & 0x01010101u;
     return (x * 0xffu) | 0x01010101u;
 }
-__device__ __forceinline__ void mm_fold(uint32_t& b0, uint32_t& b1, uint32_t key) {
-    b1 = min(b1, max(b0, key));
-    b0 = min(b0, key);
-}
 __global__ __launch_bounds__(256) void k_knn2_mfma(const uint32_t* __restrict__ q, int nq, const uint32_t* __restrict__ t, int nt,
                                                    int slice, u64* __restrict__ part, int32_t* __restrict__ arrive,
                                                    int32_t* __restrict__ out_idx, int32_t* __restrict__ out_dist) {
@@ -207,16 +203,14 @@ __global__ __launch_bounds__(256) void k_knn2_mfma(const uint32_t* __restrict__ 
             const int jl = 16 * tile + 4 * kb + r;
             const uint32_t d = (uint32_t)(256 - acc[r]) >> 1;
             const uint32_t key = jl < jn ? ((d << 16) | (uint32_t)(j0 + jl)) : 0xffffffffu;
-            mm_fold(b0, b1, key);
+            knn2_insert(b0, b1, key);
         }
     }
     // ---- the four lanes of a column
 #pragma unroll
     for (int o = 16; o <= 32; o <<= 1) {
         const uint32_t o0 = (uint32_t)__shfl_xor((int)b0, o), o1 = (uint32_t)__shfl_xor((int)b1, o);
-        const uint32_t c1 = min(max(b0, o0), min(b1, o1));
-        b0 = min(b0, o0);
-        b1 = c1;
+        knn2_fold(b0, b1, o0, o1);
     }
     // ---- slice partials -> the last workgroup of the query group folds them (arrival counter per group, self re-arming)
     u64* mine = part + ((size_t)blockIdx.y * nq + qc);
@@ -237,10 +231,7 @@ __global__ __launch_bounds__(256) void k_knn2_mfma(const uint32_t* __restrict__ 
     b0 = b1 = 0xffffffffu;
     for (int s2 = 0; s2 < (int)gridDim.y; ++s2) {
         const u64 w = __hip_atomic_load(part + ((size_t)s2 * nq + qo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t o0 = (uint32_t)w, o1 = (uint32_t)(w >> 32);
-        const uint32_t c1 = min(max(b0, o0), min(b1, o1));
-        b0 = min(b0, o0);
-        b1 = c1;
+        knn2_fold(b0, b1, (uint32_t)w, (uint32_t)(w >> 32));
     }
     const bool h0 = b0 != 0xffffffffu, h1 = b1 != 0xffffffffu;
     out_idx[2 * qo] = h0 ? (int)(b0 & 0xffffu) : -1;

@@ -188,29 +188,39 @@ struct mvo_undistort_state {  // owned by undistort_host.cpp, released through m
     size_t src_cap = 0, dst_cap = 0;
 };
 
+// what the pose-gated matchers share (guided_knn2.h: the kernel body; guided_match_host.h: the host tail)
+#define GK_MAX_GROUPS 8  // train groups of guided_knn2() (workgroups per group of 64 queries)
+struct GuidedPartials {  // the scratch as the kernels take it
+    unsigned long long* key;  // GK_MAX_GROUPS x nq partial key pairs
+    int32_t *cnt, *arrive;    // as many partial counts; one arrival counter per group of 64 queries
+};
+struct GuidedScratch {  // one per matcher; keys, counts and counters are one allocation (methods: guided_match_host.h)
+    unsigned long long* d_part = nullptr;
+    int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
+    int cap = 0;  // queries
+    int ensure(mvo_ctx* ctx, int n);  // room for n queries: max(4096, 1.5 n) when it grows, the counters zeroed on ctx->stream
+    void release();
+    GuidedPartials partials() const { return {d_part, d_part_cnt, d_arrive}; }
+};
+
 // pose-guided matching (epipolar_kernels.hip / epipolar_host.cpp)
 struct EpipolarArgs {  // k_knn2_epipolar: F row-major, x2^T F x1 = 0
     double f[9];
 };
-#define EK_MAX_GROUPS 8  // train groups of k_knn2_epipolar (workgroups per group of 64 queries)
 struct mvo_epipolar_state {  // owned by epipolar_host.cpp, released through mvo_ctx::epi_release
     uint8_t *d_q = nullptr, *d_t = nullptr;  // staging of the host-pointer form
     float *d_qxy = nullptr, *d_txy = nullptr;
     double* d_tol2 = nullptr;
-    unsigned long long* d_part = nullptr;  // EK_MAX_GROUPS x cap_q partial key pairs, then as many counts, then the arrival counters
-    int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
-    int32_t* d_out = nullptr;  // cap_q x 5: where a caller that keeps the result on the device has it delivered
+    GuidedScratch scratch;
     int cap_q = 0, cap_t = 0;
 };
 
 // tracking by projection (projection_kernels.hip / projection_host.cpp)
-#define PK_MAX_GROUPS 8  // train groups of k_map_match_projection (workgroups per group of 64 map points)
 struct mvo_projection_state {  // owned by projection_host.cpp, released through mvo_ctx::proj_release
     uint8_t* d_t = nullptr;   // staging of the host-pointer form
     double* d_tg = nullptr;   // cap_t x ((double)x, (double)y, r2): the gate's view of the frame keypoints
-    unsigned long long* d_part = nullptr;  // PK_MAX_GROUPS x cap_m partial key pairs, then as many counts, then the arrival counters
-    int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
-    int cap_m = 0, cap_t = 0;
+    GuidedScratch scratch;
+    int cap_t = 0;
 };
 
 // cell-wise FAST + quadtree spread (orb_distribute_kernels.hip / orb_distribute_host.cpp)
@@ -458,14 +468,11 @@ int undistort_launch_map(mvo_ctx* ctx, const UndistortArgs& a, int w, int h, Und
 int undistort_launch_remap(mvo_ctx* ctx, const UndistortRec* d_map, const uint8_t* d_src, int w, int h, int stride,
                            int channels, uint8_t* d_out, int out_stride);
 // epipolar_kernels.hip
-int epipolar_groups(int nt);
 int epipolar_launch_knn2(mvo_ctx* ctx, const uint8_t* d_q, const float* d_qxy, int nq, const uint8_t* d_t, const float* d_txy,
-                         const double* d_tol2, int nt, const EpipolarArgs& a, unsigned long long* d_part, int32_t* d_part_cnt,
-                         int32_t* d_arrive, int32_t* out);
+                         const double* d_tol2, int nt, const EpipolarArgs& a, GuidedPartials part, int32_t* out);
 // projection_kernels.hip
-int projection_groups(int nt);
 int projection_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, int n_map, const TrackViewArgs& a, const uint8_t* d_t,
-                      const double* d_tg, int nt, unsigned long long* d_part, int32_t* d_part_cnt, int32_t* d_arrive, int32_t* out);
+                      const double* d_tg, int nt, GuidedPartials part, int32_t* out);
 // orb_distribute_kernels.hip
 int dist_launch_cells(mvo_ctx* ctx, const DistCell* d_cells, int n_cells, int thr_min, int thr_ini, int32_t* counts,
                       DistRecord* records);

@@ -10,18 +10,17 @@
 #include <string>
 #include <vector>
 
-#include "mvo_internal.h"
+#include "guided_match_host.h"
 
 namespace {
-
-const int kMaxTrains = 65535;  // the train index lives in the low 16 bits of a key
 
 void projection_release(mvo_ctx* ctx) {
     mvo_projection_state* e = ctx->proj;
     if (!e) return;
-    void* dev[] = {e->d_t, e->d_tg, e->d_part};
+    void* dev[] = {e->d_t, e->d_tg};
     for (void* p : dev)
         if (p) mvo_free_on_current_device(p);
+    e->scratch.release();
     delete e;
     ctx->proj = nullptr;
 }
@@ -32,19 +31,7 @@ int ensure_bufs(mvo_ctx* ctx, int n_map, int nt) {
         ctx->proj_release = projection_release;
     }
     mvo_projection_state* e = ctx->proj;
-    if (n_map > e->cap_m) {
-        if (e->d_part) mvo_free_on_current_device(e->d_part);
-        e->d_part = nullptr;
-        e->cap_m = 0;
-        const size_t cap = (size_t)std::max(4096, n_map + n_map / 2);
-        // partial key pairs, partial counts, one arrival counter per group of 64 map points (self re-arming, zeroed once)
-        const size_t keys = PK_MAX_GROUPS * cap * 8, cnts = PK_MAX_GROUPS * cap * 4, ctr = (cap / 64 + 2) * 4;
-        MVO_HIP(hipMalloc((void**)&e->d_part, keys + cnts + ctr));
-        e->d_part_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys);
-        e->d_arrive = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(e->d_part) + keys + cnts);
-        MVO_HIP(hipMemsetAsync(e->d_arrive, 0, ctr, ctx->stream));
-        e->cap_m = (int)cap;
-    }
+    if (int r = e->scratch.ensure(ctx, n_map)) return r;
     if (nt > e->cap_t) {
         void* old[] = {e->d_t, e->d_tg};
         for (void* p : old)
@@ -66,8 +53,8 @@ int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, d
         const void* t, bool t_on_device, const float* txy, const float* t_scale, int nt, double max_px, float* px, int32_t* idx,
         int32_t* dist, int32_t* n_candidates, const char* who) {
     if (!ctx) return MVO_ERR_INVALID;
-    auto invalid = [&](const char* what, int code = MVO_ERR_INVALID) {  // the message names the entry point the caller used
-        return mvo_set_err(ctx, code, (std::string(who) + ": " + what).c_str(), hipSuccess);
+    auto invalid = [&](const char* what) {  // the message names the entry point the caller used
+        return mvo_set_err(ctx, MVO_ERR_INVALID, (std::string(who) + ": " + what).c_str(), hipSuccess);
     };
     if (!map || !T_w_c || nt < 0 || (nt && (!t || !txy)) || (map->n && (!idx || !dist)))
         return invalid("bad arguments");
@@ -80,11 +67,7 @@ int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, d
         return invalid("fx or fy 0, or intrinsics not finite");
     if (cols <= 0 || rows <= 0) return invalid("cols or rows <= 0");
     if (!(max_px >= 0)) return invalid("max_px negative or NaN");
-    if (nt > kMaxTrains) return invalid("more than 65535 train descriptors", MVO_ERR_CAPACITY);
-    if (t_scale)
-        for (int j = 0; j < nt; ++j)
-            if (!std::isfinite(t_scale[j]) || t_scale[j] < 0)
-                return invalid("t_scale entry negative or not finite");
+    if (int r = guided_check_trains(ctx, who, t_scale, nt)) return r;
     const int n_map = map->n;
     if (n_map == 0) return MVO_OK;
     TrackViewArgs a;
@@ -103,10 +86,9 @@ int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, d
     int32_t* h_out = reinterpret_cast<int32_t*>(ctx->h_pin);
     double* h_tg = reinterpret_cast<double*>(ctx->h_pin + out_bytes);
     for (int j = 0; j < nt; ++j) {
-        const double rj = max_px * (t_scale ? (double)t_scale[j] : 1.0);
         h_tg[3 * j] = (double)txy[2 * j];
         h_tg[3 * j + 1] = (double)txy[2 * j + 1];
-        h_tg[3 * j + 2] = rj * rj;
+        h_tg[3 * j + 2] = guided_tol2(max_px, t_scale, j);
     }
     const uint8_t* d_t = static_cast<const uint8_t*>(t);
     if (nt) {
@@ -117,7 +99,7 @@ int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, d
         }
     }
     ExtractGate gate(ctx);
-    if ((r = projection_launch(ctx, map->d_pos, map->d_desc, n_map, a, d_t, e->d_tg, nt, e->d_part, e->d_part_cnt, e->d_arrive, h_out)))
+    if ((r = projection_launch(ctx, map->d_pos, map->d_desc, n_map, a, d_t, e->d_tg, nt, e->scratch.partials(), h_out)))
         return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));
     gate.release();
@@ -175,22 +157,7 @@ int mvo_map_match_features_projection(mvo_ctx* ctx, mvo_map* map, const double* 
     if (r) return r;
     if (in_view)
         for (int i = 0; i < n1; ++i) in_view[i] = cand[i] >= 0 ? 1 : 0;
-    // per train the claiming query with the smallest (distance, queryIdx); queries arrive in ascending order
-    std::vector<int32_t> owner(nt > 0 ? nt : 1, -1);
-    for (int i = 0; i < n1; ++i) {
-        const int j = idx[2 * i], d0 = dist[2 * i];
-        if (j < 0 || d0 > max_hamming) continue;
-        if (idx[2 * i + 1] >= 0 && !((double)d0 < lowe_ratio * (double)dist[2 * i + 1])) continue;
-        if (owner[j] < 0 || d0 < dist[2 * owner[j]]) owner[j] = i;
-    }
-    int cnt = 0;
-    for (int j = 0; j < nt; ++j) cnt += owner[j] >= 0 ? 1 : 0;
-    *n = cnt;
-    if (cnt > cap || (cnt && !out)) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "match buffer too small", hipSuccess);
-    int k = 0;
-    for (int j = 0; j < nt; ++j)
-        if (owner[j] >= 0) out[k++] = {owner[j], j, 0, (float)dist[2 * owner[j]]};
-    return MVO_OK;
+    return guided_filter_matches(ctx, idx.data(), dist.data(), n1, nt, lowe_ratio, max_hamming, out, cap, n);
 }
 
 // map.h:19 (Map::map_points_.size() of the resident copy): the number of rows the calls above write

@@ -4,5 +4,6 @@
 # every lane of k_map_refresh runs as a fiber on the CPU.
 #   make -C tests/sim -f map_refresh.mk _build/libmvo_sim_map_refresh.so
 include orb_distribute.mk
-_build/libmvo_sim_map_refresh.so: $(FULL_OBJ) _build/full/init_host.cpp.o _build/full/undistort_host.cpp.o _build/full/undistort_kernels.hip.o _build/full/epipolar_host.cpp.o _build/full/epipolar_kernels.hip.o _build/full/projection_host.cpp.o _build/full/projection_kernels.hip.o _build/full/orb_distribute_host.cpp.o _build/full/orb_distribute_kernels.hip.o _build/full/map_refresh_host.cpp.o _build/full/map_refresh_kernels.hip.o
+MAP_REFRESH_OBJ := $(ORB_DISTRIBUTE_OBJ) _build/full/map_refresh_host.cpp.o _build/full/map_refresh_kernels.hip.o
+_build/libmvo_sim_map_refresh.so: $(MAP_REFRESH_OBJ)
 	$(CXX) -shared -fPIC -pthread -o $@ $^

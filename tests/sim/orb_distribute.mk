@@ -4,6 +4,7 @@
 # rule: every lane of k_fast_cells and k_ic_angle runs as a fiber on the CPU.
 #   make -C tests/sim -f orb_distribute.mk _build/libmvo_sim_orb_distribute.so
 include projection.mk
-_build/libmvo_sim_orb_distribute.so: $(FULL_OBJ) _build/full/init_host.cpp.o _build/full/undistort_host.cpp.o _build/full/undistort_kernels.hip.o _build/full/epipolar_host.cpp.o _build/full/epipolar_kernels.hip.o _build/full/projection_host.cpp.o _build/full/projection_kernels.hip.o _build/full/orb_distribute_host.cpp.o _build/full/orb_distribute_kernels.hip.o
+ORB_DISTRIBUTE_OBJ := $(PROJECTION_OBJ) _build/full/orb_distribute_host.cpp.o _build/full/orb_distribute_kernels.hip.o
+_build/libmvo_sim_orb_distribute.so: $(ORB_DISTRIBUTE_OBJ)
 	$(CXX) -shared -fPIC -pthread -o $@ $^
 _build/full/orb_kernels.hip.o _build/full/orb_distribute_kernels.hip.o: $(CSRC)/orb_device.h

@@ -4,5 +4,6 @@
 # every lane of k_map_match_projection runs as a fiber on the CPU.
 #   make -C tests/sim -f projection.mk _build/libmvo_sim_projection.so
 include epipolar.mk
-_build/libmvo_sim_projection.so: $(FULL_OBJ) _build/full/init_host.cpp.o _build/full/undistort_host.cpp.o _build/full/undistort_kernels.hip.o _build/full/epipolar_host.cpp.o _build/full/epipolar_kernels.hip.o _build/full/projection_host.cpp.o _build/full/projection_kernels.hip.o
+PROJECTION_OBJ := $(EPIPOLAR_OBJ) _build/full/projection_host.cpp.o _build/full/projection_kernels.hip.o
+_build/libmvo_sim_projection.so: $(PROJECTION_OBJ)
 	$(CXX) -shared -fPIC -pthread -o $@ $^

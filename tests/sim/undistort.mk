@@ -4,5 +4,6 @@
 # compiled for x86 against hip_emu/ by the same pattern rule.
 #   make -C tests/sim -f undistort.mk _build/libmvo_sim_undistort.so
 include init_finish.mk
-_build/libmvo_sim_undistort.so: $(FULL_OBJ) _build/full/init_host.cpp.o _build/full/undistort_host.cpp.o _build/full/undistort_kernels.hip.o
+UNDISTORT_OBJ := $(INIT_OBJ) _build/full/undistort_host.cpp.o _build/full/undistort_kernels.hip.o
+_build/libmvo_sim_undistort.so: $(UNDISTORT_OBJ)
 	$(CXX) -shared -fPIC -pthread -o $@ $^

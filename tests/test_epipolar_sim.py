@@ -73,6 +73,10 @@ def test_device_pointer_form_and_the_largest_train_set_on_the_emulated_build(sim
     T.test_the_largest_train_set(simmvo, simctx)
 
 
+def test_partial_scratch_regrow_on_the_emulated_build(simmvo):
+    T.test_partial_scratch_regrows_between_calls(simmvo)
+
+
 def test_errors_and_fundamental_from_poses_on_the_emulated_build(simmvo, simctx):
     T.test_errors(simmvo, simctx)
     T.test_fundamental_from_poses(simmvo)

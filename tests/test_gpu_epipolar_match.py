@@ -234,6 +234,19 @@ def test_the_largest_train_set(mvo, ctx):
     assert_raw_equal((idx, dist, cnt), E.knn2(q, qxy, t, txy, F_ROW, 0.25), "65535 trains")
 
 
+def test_partial_scratch_regrows_between_calls(mvo):
+    """One context of its own, three raw calls: 64 x 300 (two train groups, so the arrival counters are used), 4200 x 300
+    (past the 4096 floor: the partial scratch is freed, reallocated and its counters zeroed again), 64 x 300 again."""
+    c = mvo.Context(0)
+    try:
+        for nq in (64, 4200, 64):
+            q, qxy, t, txy, F, px, scale, want = raw_inputs(mvo, nq, 300, "perturbed", True)
+            assert 0 < want[2].sum() < nq * 300
+            assert_raw_equal(c.match_knn2_epipolar(q, qxy, t, txy, F, px, scale), want, "%d x 300" % nq)
+    finally:
+        c.close()
+
+
 def test_fundamental_from_poses(mvo):
     rng = np.random.RandomState(21)
     for k in range(8):

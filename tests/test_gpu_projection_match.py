@@ -214,6 +214,20 @@ def test_the_largest_train_set(ctx):
     assert_raw_equal(got, P.knn2(pos, desc, I4, K, COLS, ROWS, t, txy, 0.25), "65535 keypoints")
 
 
+def test_partial_scratch_regrows_between_calls(mvo):
+    """One context of its own, three raw calls: 64 x 300 (two train groups, so the arrival counters are used), 4200 x 300
+    (past the 4096 floor: the partial scratch is freed, reallocated and its counters zeroed again), 64 x 300 again."""
+    c = mvo.Context(0)
+    try:
+        for n_map in (64, 4200, 64):
+            pos, desc, T, t, txy, r, scale, want = raw_inputs(mvo, n_map, 300, "perturbed", True)
+            assert (want[3] > 0).any() and (want[3] == -1).any()
+            with resident(c, pos, desc) as m:
+                assert_raw_equal(c.map_match_knn2_projection(m, T, P.FR1_K, COLS, ROWS, t, txy, r, scale), want, "%d x 300" % n_map)
+    finally:
+        c.close()
+
+
 def test_errors(mvo, ctx):
     pos, desc, T, t, txy, r, scale, want = raw_inputs(mvo, 63, 17, "perturbed", True)
     lib, h, K = ctx.lib, ctx.h, P.FR1_K

@@ -75,6 +75,10 @@ def test_device_pointer_form_moved_positions_and_the_largest_train_set_on_the_em
     T.test_the_largest_train_set(simctx)
 
 
+def test_partial_scratch_regrow_on_the_emulated_build(simmvo):
+    T.test_partial_scratch_regrows_between_calls(simmvo)
+
+
 def test_errors_and_predict_pose_on_the_emulated_build(simmvo, simctx):
     T.test_errors(simmvo, simctx)
     T.test_predict_pose(simmvo)
