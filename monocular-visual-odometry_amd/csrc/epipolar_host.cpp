@@ -14,13 +14,7 @@
 namespace {
 
 void epipolar_release(mvo_ctx* ctx) {
-    mvo_epipolar_state* e = ctx->epi;
-    if (!e) return;
-    void* dev[] = {e->d_q, e->d_qxy, e->d_t, e->d_txy, e->d_tol2};
-    for (void* p : dev)
-        if (p) mvo_free_on_current_device(p);
-    e->scratch.release();
-    delete e;
+    delete ctx->epi;
     ctx->epi = nullptr;
 }
 
@@ -30,30 +24,11 @@ int ensure_bufs(mvo_ctx* ctx, int nq, int nt) {
         ctx->epi_release = epipolar_release;
     }
     mvo_epipolar_state* e = ctx->epi;
-    if (nq > e->cap_q) {
-        void* old[] = {e->d_q, e->d_qxy};
-        for (void* p : old)
-            if (p) mvo_free_on_current_device(p);
-        e->d_q = nullptr, e->d_qxy = nullptr;
-        e->cap_q = 0;
-        const size_t cap = (size_t)std::max(4096, nq + nq / 2);
-        MVO_HIP(hipMalloc((void**)&e->d_q, cap * 32));
-        MVO_HIP(hipMalloc((void**)&e->d_qxy, cap * 8));
-        e->cap_q = (int)cap;
-    }
-    if (int r = e->scratch.ensure(ctx, nq)) return r;  // (grows when cap_q does: the same rule)
-    if (nt > e->cap_t) {
-        void* old[] = {e->d_t, e->d_txy, e->d_tol2};
-        for (void* p : old)
-            if (p) mvo_free_on_current_device(p);
-        e->d_t = nullptr, e->d_txy = nullptr, e->d_tol2 = nullptr;
-        e->cap_t = 0;
-        const size_t cap = (size_t)std::max(4096, nt + nt / 2);
-        MVO_HIP(hipMalloc((void**)&e->d_t, cap * 32));
-        MVO_HIP(hipMalloc((void**)&e->d_txy, cap * 8));
-        MVO_HIP(hipMalloc((void**)&e->d_tol2, cap * 8));
-        e->cap_t = (int)cap;
-    }
+    int r;
+    if ((r = e->d_q.ensure(ctx, (size_t)nq * 32, 4096 * 32)) || (r = e->d_qxy.ensure(ctx, (size_t)nq * 2, 4096 * 2)) ||
+        (r = e->scratch.ensure(ctx, nq)) || (r = e->d_t.ensure(ctx, (size_t)nt * 32, 4096 * 32)) ||
+        (r = e->d_txy.ensure(ctx, (size_t)nt * 2, 4096 * 2)) || (r = e->d_tol2.ensure(ctx, nt, 4096)))
+        return r;
     return MVO_OK;
 }
 

@@ -12,7 +12,7 @@
 #include "mvo_internal.h"
 
 inline void GuidedScratch::release() {
-    if (d_part) mvo_free_on_current_device(d_part);
+    buf.release();
     d_part = nullptr, d_part_cnt = nullptr, d_arrive = nullptr;
     cap = 0;
 }
@@ -23,9 +23,10 @@ inline int GuidedScratch::ensure(mvo_ctx* ctx, int n) {
     const size_t c = (size_t)std::max(4096, n + n / 2);
     // partial key pairs, partial counts, one arrival counter per group of 64 queries (self re-arming, zeroed once)
     const size_t keys = GK_MAX_GROUPS * c * 8, cnts = GK_MAX_GROUPS * c * 4, ctr = (c / 64 + 2) * 4;
-    MVO_HIP(hipMalloc((void**)&d_part, keys + cnts + ctr));
-    d_part_cnt = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(d_part) + keys);
-    d_arrive = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(d_part) + keys + cnts);
+    if (int r = buf.ensure_exact(ctx, keys + cnts + ctr)) return r;
+    d_part = reinterpret_cast<unsigned long long*>(buf.p);
+    d_part_cnt = reinterpret_cast<int32_t*>(buf.p + keys);
+    d_arrive = reinterpret_cast<int32_t*>(buf.p + keys + cnts);
     MVO_HIP(hipMemsetAsync(d_arrive, 0, ctr, ctx->stream));
     cap = (int)c;
     return MVO_OK;

@@ -11,10 +11,7 @@
 namespace {
 
 void refresh_release(mvo_ctx* ctx) {
-    mvo_refresh_state* e = ctx->refresh;
-    if (!e) return;
-    if (e->d_in) mvo_free_on_current_device(e->d_in);
-    delete e;
+    delete ctx->refresh;
     ctx->refresh = nullptr;
 }
 
@@ -23,16 +20,7 @@ int ensure_bufs(mvo_ctx* ctx, size_t bytes) {
         ctx->refresh = new mvo_refresh_state();
         ctx->refresh_release = refresh_release;
     }
-    mvo_refresh_state* e = ctx->refresh;
-    if (bytes > e->cap) {
-        if (e->d_in) mvo_free_on_current_device(e->d_in);
-        e->d_in = nullptr;
-        e->cap = 0;
-        const size_t cap = std::max<size_t>(1 << 20, bytes + bytes / 2);
-        MVO_HIP(hipMalloc((void**)&e->d_in, cap));
-        e->cap = cap;
-    }
-    return MVO_OK;
+    return ctx->refresh->d_in.ensure(ctx, bytes, (size_t)1 << 20);
 }
 
 inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
@@ -81,7 +69,7 @@ int mvo_map_refresh(mvo_ctx* ctx, mvo_map* map, const uint8_t* obs_desc, const d
     uint8_t* h_desc = ctx->h_pin + norm_b;
     int32_t* h_choice = reinterpret_cast<int32_t*>(ctx->h_pin + norm_b + desc_b);
     ExtractGate gate(ctx);
-    if ((r = map_refresh_launch(ctx, map->d_pos, map->d_desc, n, e->d_in + cam_b, reinterpret_cast<const double*>(e->d_in),
+    if ((r = map_refresh_launch(ctx, map->d_pos, map->d_desc, n, e->d_in + cam_b, reinterpret_cast<const double*>(e->d_in.p),
                                 reinterpret_cast<const int32_t*>(e->d_in + cam_b + odesc_b), h_choice, h_desc, h_norm)))
         return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));

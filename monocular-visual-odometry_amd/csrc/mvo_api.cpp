@@ -93,6 +93,13 @@ void ExtractGate::release() {
     device = -1;
 }
 
+int mvo_stage_image(mvo_ctx* ctx, const uint8_t* img, int h, int stride) {
+    const size_t bytes = (size_t)h * stride;
+    if (int r = ctx->d_img.ensure_exact(ctx, bytes, 64)) return r;
+    MVO_HIP(hipMemcpyAsync(ctx->d_img, img, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return MVO_OK;
+}
+
 static int g_match_host_out = 1;  // measurement knob: 0 = k_knn2 delivers into HBM, a copy follows
 
 extern "C" {
@@ -180,10 +187,9 @@ void mvo_destroy(mvo_ctx* ctx) {
     if (ctx->dist_release) ctx->dist_release(ctx);
     if (ctx->refresh_release) ctx->refresh_release(ctx);
     ba_pool_release(ctx);
-    void* dev[] = {ctx->d_img, ctx->d_raw,  ctx->d_blur, ctx->d_tabs, ctx->d_pyr_regs,
-                   ctx->d_kp,   ctx->d_desc_buf, ctx->d_mq,    ctx->d_mt,   ctx->d_mqxy,      ctx->d_mtxy,
-                   ctx->d_mout, ctx->d_fh_slots, ctx->d_fh_line, ctx->d_fh_arrive};
-    for (void* p : dev)
+    ctx->d_img.release(), ctx->d_mq.release(), ctx->d_mt.release(), ctx->d_mqxy.release(), ctx->d_mtxy.release(), ctx->d_mout.release();
+    void* dev[] = {ctx->d_raw, ctx->d_blur, ctx->d_tabs, ctx->d_pyr_regs, ctx->d_kp, ctx->d_desc_buf, ctx->d_fh_slots, ctx->d_fh_line, ctx->d_fh_arrive};
+    for (void* p : dev)  // (the geometry set of orb_host.cpp)
         if (p) mvo_free_on_current_device(p);
     if (ctx->h_pin) ba_service_free(ctx->device, ctx->h_pin, true);
     for (auto& p : ctx->prof_pending) ctx->prof_pool.push_back(p.second);
@@ -226,19 +232,6 @@ static int check_image(mvo_ctx* ctx, const void* img, int w, int h, int stride, 
     return MVO_OK;
 }
 
-static int upload_image(mvo_ctx* ctx, const uint8_t* img, int h, int stride) {
-    const size_t bytes = (size_t)h * stride;
-    if (ctx->d_img_cap < bytes) {
-        if (ctx->d_img) ba_service_free(ctx->device, ctx->d_img, false);
-        ctx->d_img = nullptr;
-        ctx->d_img_cap = 0;
-        MVO_HIP(hipMalloc((void**)&ctx->d_img, bytes + 64));
-        ctx->d_img_cap = bytes;
-    }
-    MVO_HIP(hipMemcpyAsync(ctx->d_img, img, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return MVO_OK;
-}
-
 static int calc_keypoints_common(mvo_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, int ch,
                                  mvo_keypoint* kps, int cap, int* n) {
     std::vector<mvo_keypoint> v;
@@ -258,7 +251,7 @@ int mvo_calc_keypoints(mvo_ctx* ctx, const uint8_t* image, int w, int h, int str
     if (r) return r;
     if (!kps || !n) return mvo_set_err(ctx, MVO_ERR_INVALID, "null output", hipSuccess);
     MVO_HIP(hipSetDevice(ctx->device));
-    if ((r = upload_image(ctx, image, h, stride))) return r;
+    if ((r = mvo_stage_image(ctx, image, h, stride))) return r;
     return calc_keypoints_common(ctx, ctx->d_img, w, h, stride, ch, kps, cap, n);
 }
 
@@ -303,7 +296,7 @@ int mvo_calc_descriptors(mvo_ctx* ctx, const uint8_t* image, int w, int h, int s
         if ((r = orb_setup_geometry(ctx, w, h))) return r;
         if (need > ctx->pyr.nlevels)
             return mvo_set_err(ctx, MVO_ERR_INVALID, "keypoint octave exceeds level_pyramid", hipSuccess);
-        if ((r = upload_image(ctx, image, h, stride))) return r;
+        if ((r = mvo_stage_image(ctx, image, h, stride))) return r;
         ctx->pyr_valid = ctx->blur_valid = false;
         if ((r = orb_launch_pyramid(ctx, ctx->d_img, stride, ch, need))) return r;
         ctx->pyr_levels_built = need;
@@ -352,34 +345,18 @@ int mvo_select_uniform_kpts_by_grid(mvo_ctx* ctx, mvo_keypoint* kps, int* n, int
 
 // ---------------------------------------------------------------------------------------------- matching
 static int ensure_match_bufs(mvo_ctx* ctx, int nq, int nt) {
-    if (nq > ctx->m_cap_q) {
-        if (ctx->d_mq) ba_service_free(ctx->device, ctx->d_mq, false);
-        if (ctx->d_mqxy) ba_service_free(ctx->device, ctx->d_mqxy, false);
-        if (ctx->d_mout) ba_service_free(ctx->device, ctx->d_mout, false);
-        ctx->d_mq = nullptr;
-        ctx->d_mqxy = nullptr;
-        ctx->d_mout = nullptr;
-        ctx->m_cap_q = 0;
-        int cap = std::max(4096, nq + nq / 2);
-        MVO_HIP(hipMalloc((void**)&ctx->d_mq, (size_t)cap * 32));
-        MVO_HIP(hipMalloc((void**)&ctx->d_mqxy, (size_t)cap * 8));
-        // results + up to 64 slices of partials + one arrival counter per group of 64 queries (self re-arming, zeroed once)
-        const size_t body = (size_t)cap * (16 + 64 * 16), ctr = ((size_t)cap / 64 + 2) * 4;
-        MVO_HIP(hipMalloc((void**)&ctx->d_mout, body + ctr));
-        ctx->d_marrive = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ctx->d_mout) + body);
-        MVO_HIP(hipMemsetAsync(ctx->d_marrive, 0, ctr, ctx->stream));
-        ctx->m_cap_q = cap;
-    }
-    if (nt > ctx->m_cap_t) {
-        if (ctx->d_mt) ba_service_free(ctx->device, ctx->d_mt, false);
-        if (ctx->d_mtxy) ba_service_free(ctx->device, ctx->d_mtxy, false);
-        ctx->d_mt = nullptr;
-        ctx->d_mtxy = nullptr;
-        ctx->m_cap_t = 0;
-        int cap = std::max(4096, nt + nt / 2);
-        MVO_HIP(hipMalloc((void**)&ctx->d_mt, (size_t)cap * 32));
-        MVO_HIP(hipMalloc((void**)&ctx->d_mtxy, (size_t)cap * 8));
-        ctx->m_cap_t = cap;
+    int r;
+    if ((r = ctx->d_mq.ensure(ctx, (size_t)nq * 32, 4096 * 32)) || (r = ctx->d_mqxy.ensure(ctx, (size_t)nq * 2, 4096 * 2)) ||
+        (r = ctx->d_mt.ensure(ctx, (size_t)nt * 32, 4096 * 32)) || (r = ctx->d_mtxy.ensure(ctx, (size_t)nt * 2, 4096 * 2)))
+        return r;
+    // results + up to 64 slices of partials (260 ints per query), then one arrival counter per group of 64 queries (self
+    // re-arming, zeroed once)
+    auto ints = [](size_t q) { return q * 260 + q / 64 + 2; };
+    if (ints(nq) > ctx->d_mout.cap) {
+        const size_t cap = (size_t)std::max(4096, nq + nq / 2);
+        if ((r = ctx->d_mout.ensure_exact(ctx, ints(cap)))) return r;
+        ctx->d_marrive = ctx->d_mout + cap * 260;
+        MVO_HIP(hipMemsetAsync(ctx->d_marrive, 0, (cap / 64 + 2) * 4, ctx->stream));
     }
     return MVO_OK;
 }

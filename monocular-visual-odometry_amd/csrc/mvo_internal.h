@@ -23,6 +23,7 @@
 #define MVO_OPAQUE(x) (void)(x)
 #endif
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +33,57 @@
 #include <vector>
 
 #include "../../include/mvo_hip.h"
+
+struct mvo_ctx;
+int mvo_set_err(mvo_ctx* c, int code, const char* what, hipError_t e);
+#define MVO_HIP(call)                                                            \
+    do {                                                                         \
+        hipError_t e__ = (call);                                                 \
+        if (e__ != hipSuccess) {                                                 \
+            (void)hipGetLastError(); /* clear the sticky error */                \
+            return mvo_set_err(ctx, MVO_ERR_HIP, #call, e__);                    \
+        }                                                                        \
+    } while (0)
+
+// hipFree / hipHostFree with the resident solver grid of `device` taken off first (both synchronise with every stream of the
+// device; the grid never ends on its own)
+void ba_service_free(int device, void* p, bool host);
+inline void mvo_free_on_current_device(void* p) {
+    int d = 0;
+    (void)hipGetDevice(&d);
+    ba_service_free(d, p, false);
+}
+
+// One grow-on-demand device buffer: a pointer and its capacity in elements, owned once.  release() frees through
+// mvo_free_on_current_device, so an owner is destroyed only on the paths that have made ctx->device current: mvo_destroy
+// with its *_release hooks, and mvo_map_release.  Neither ensure preserves the contents.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    operator T*() const { return p; }
+    void release() {
+        if (p) mvo_free_on_current_device(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // room for exactly n elements plus pad_bytes: the fixed-size buffers and the image staging
+    int ensure_exact(mvo_ctx* ctx, size_t n, size_t pad_bytes = 0) {
+        if (n <= cap) return MVO_OK;
+        release();
+        void* q = nullptr;
+        MVO_HIP(hipMalloc(&q, n * sizeof(T) + pad_bytes));
+        p = static_cast<T*>(q);  // (pointer and capacity are set only once the allocation stands)
+        cap = n;
+        return MVO_OK;
+    }
+    // room for n elements, max(floor, n + n / 2) when it grows: everything sized by a count of matches or points
+    int ensure(mvo_ctx* ctx, size_t n, size_t floor) { return n <= cap ? MVO_OK : ensure_exact(ctx, std::max(floor, n + n / 2)); }
+};
 
 #define MVO_MAX_LEVELS 8
 #define MVO_BORDER 32  // ORB: max(edgeThreshold 31, descPatchSize 22, HARRIS_BLOCK/2) + 1
@@ -163,9 +215,9 @@ struct TrackViewArgs {
 };
 struct mvo_track_state;  // device buffers of the tracking rows, allocated on first use
 struct mvo_map {  // the resident map (mvo_map_*, track_host.cpp): n x 3 f32 positions, n x 32 descriptor bytes
-    float* d_pos = nullptr;
-    uint8_t* d_desc = nullptr;
-    int n = 0, cap = 0;
+    DevBuf<float> d_pos;
+    DevBuf<uint8_t> d_desc;
+    int n = 0;
 };
 
 // undistortion (undistort_kernels.hip / undistort_host.cpp)
@@ -182,10 +234,8 @@ struct mvo_undistort_state {  // owned by undistort_host.cpp, released through m
     bool configured = false;
     mvo_undistort_params params{};  // as configured, coefficients beyond n_coeffs zeroed
     int w = 0, h = 0;
-    UndistortRec* d_map = nullptr;
-    size_t map_cap = 0;  // records
-    uint8_t *d_src = nullptr, *d_dst = nullptr;  // staging of the host-pointer form
-    size_t src_cap = 0, dst_cap = 0;
+    DevBuf<UndistortRec> d_map;
+    DevBuf<uint8_t> d_src, d_dst;  // staging of the host-pointer form
 };
 
 // what the pose-gated matchers share (guided_knn2.h: the kernel body; guided_match_host.h: the host tail)
@@ -195,7 +245,8 @@ struct GuidedPartials {  // the scratch as the kernels take it
     int32_t *cnt, *arrive;    // as many partial counts; one arrival counter per group of 64 queries
 };
 struct GuidedScratch {  // one per matcher; keys, counts and counters are one allocation (methods: guided_match_host.h)
-    unsigned long long* d_part = nullptr;
+    DevBuf<uint8_t> buf;
+    unsigned long long* d_part = nullptr;  // views into buf
     int32_t *d_part_cnt = nullptr, *d_arrive = nullptr;
     int cap = 0;  // queries
     int ensure(mvo_ctx* ctx, int n);  // room for n queries: max(4096, 1.5 n) when it grows, the counters zeroed on ctx->stream
@@ -208,19 +259,17 @@ struct EpipolarArgs {  // k_knn2_epipolar: F row-major, x2^T F x1 = 0
     double f[9];
 };
 struct mvo_epipolar_state {  // owned by epipolar_host.cpp, released through mvo_ctx::epi_release
-    uint8_t *d_q = nullptr, *d_t = nullptr;  // staging of the host-pointer form
-    float *d_qxy = nullptr, *d_txy = nullptr;
-    double* d_tol2 = nullptr;
+    DevBuf<uint8_t> d_q, d_t;  // staging of the host-pointer form
+    DevBuf<float> d_qxy, d_txy;
+    DevBuf<double> d_tol2;
     GuidedScratch scratch;
-    int cap_q = 0, cap_t = 0;
 };
 
 // tracking by projection (projection_kernels.hip / projection_host.cpp)
 struct mvo_projection_state {  // owned by projection_host.cpp, released through mvo_ctx::proj_release
-    uint8_t* d_t = nullptr;   // staging of the host-pointer form
-    double* d_tg = nullptr;   // cap_t x ((double)x, (double)y, r2): the gate's view of the frame keypoints
+    DevBuf<uint8_t> d_t;  // staging of the host-pointer form
+    DevBuf<double> d_tg;  // nt x ((double)x, (double)y, r2): the gate's view of the frame keypoints
     GuidedScratch scratch;
-    int cap_t = 0;
 };
 
 // cell-wise FAST + quadtree spread (orb_distribute_kernels.hip / orb_distribute_host.cpp)
@@ -253,8 +302,8 @@ struct mvo_orb_distribute_state {  // owned by orb_distribute_host.cpp, released
     DistLevel lv[MVO_MAX_LEVELS] = {};
     size_t n_records = 0;  // sum of the slot capacities
     int kp_cap = 0;        // most key points a frame can keep (quota + 2 per level, or the initial nodes)
-    DistCell* d_cells = nullptr;
-    signed char* d_disc = nullptr;  // (u, v) of the 749 pixels of the IC-angle disc
+    DevBuf<DistCell> d_cells;
+    DevBuf<signed char> d_disc;  // (u, v) of the 749 pixels of the IC-angle disc
     int disc_n = 0;
     std::vector<mvo_distribute_candidate> last_cand;  // step 5 of the last call (debug getter)
 };
@@ -262,8 +311,7 @@ struct mvo_orb_distribute_state {  // owned by orb_distribute_host.cpp, released
 // map points refreshed from their observations (map_refresh_kernels.hip / map_refresh_host.cpp)
 #define MR_MAX_OBS 64  // observations per map point: one lane each
 struct mvo_refresh_state {  // owned by map_refresh_host.cpp, released through mvo_ctx::refresh_release
-    uint8_t* d_in = nullptr;  // one upload per call: the camera centres, the descriptors, the n + 1 starts
-    size_t cap = 0;           // bytes
+    DevBuf<uint8_t> d_in;  // one upload per call: the camera centres, the descriptors, the n + 1 starts
 };
 
 struct ProfEntry {
@@ -276,7 +324,6 @@ struct ProfEntry {
 // the CUs the resident solver grid leaves free; their combined throughput DROPS when too many frames interleave there
 // (round 4: 14 frames at once -> 3400 frames/s of extraction, 8-9 at once -> 4600), so the excess waits at the door.
 extern std::atomic<int> g_extract_concurrency;
-struct mvo_ctx;
 struct ExtractGate {
     int device = -1;
     explicit ExtractGate(const mvo_ctx* ctx);
@@ -307,8 +354,7 @@ struct mvo_ctx {
     bool pyr_group_tiled[MVO_MAX_LEVELS] = {false};  // per level group: every tile's regions fit the LDS pool
     int pyr_group_lds[MVO_MAX_LEVELS] = {0};         // ... and the bytes of it the hungriest tile of the group needs
     int pyr_levels_built = 0;
-    uint8_t* d_img = nullptr;
-    size_t d_img_cap = 0;
+    DevBuf<uint8_t> d_img;  // image staging of the host-pointer forms (mvo_stage_image)
     uint8_t *d_raw = nullptr, *d_blur = nullptr;
     size_t pyr_bytes = 0;
     ResizeEntry* d_tabs = nullptr;
@@ -328,11 +374,10 @@ struct mvo_ctx {
     size_t h_pin_cap = 0;
     hipEvent_t ev = nullptr;
     // --- matcher
-    uint8_t *d_mq = nullptr, *d_mt = nullptr;
-    float *d_mqxy = nullptr, *d_mtxy = nullptr;
-    int32_t* d_mout = nullptr;
+    DevBuf<uint8_t> d_mq, d_mt;
+    DevBuf<float> d_mqxy, d_mtxy;
+    DevBuf<int32_t> d_mout;
     int32_t* d_marrive = nullptr;  // k_knn2 arrival counters (inside the d_mout allocation)
-    int m_cap_q = 0, m_cap_t = 0;
     // --- tracking rows
     mvo_track_state* track = nullptr;
     // record of the last mvo_init_two_view (init_host.cpp; mvo_debug_get_init_finish)
@@ -369,15 +414,6 @@ struct mvo_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
 };
 
-int mvo_set_err(mvo_ctx* c, int code, const char* what, hipError_t e);
-#define MVO_HIP(call)                                                            \
-    do {                                                                         \
-        hipError_t e__ = (call);                                                 \
-        if (e__ != hipSuccess) {                                                 \
-            (void)hipGetLastError(); /* clear the sticky error */                \
-            return mvo_set_err(ctx, MVO_ERR_HIP, #call, e__);                    \
-        }                                                                        \
-    } while (0)
 
 // profiling brackets
 void mvo_prof_begin(mvo_ctx* c, const char* name);
@@ -417,6 +453,8 @@ struct HostTimes {
 };
 
 int mvo_ensure_pinned(mvo_ctx* ctx, size_t bytes);
+// h rows of `stride` bytes from the host into ctx->d_img, on ctx->stream (mvo_api.cpp)
+int mvo_stage_image(mvo_ctx* ctx, const uint8_t* img, int h, int stride);
 
 // orb_kernels.hip
 int orb_launch_pyramid(mvo_ctx* ctx, const uint8_t* d_img, int stride, int channels, int nlevels);
@@ -488,7 +526,7 @@ void track_release(mvo_ctx* ctx);
 // What the last mvo_estimate_possible_relative_poses(n matches) of this ctx left on the device, for the finish of the
 // initialisation (init_host.cpp): the matched pixels, the E list followed by the H list, k_recover_pose's and
 // k_h_decompose's outputs and k_init_triangulate's [5][n] points; and out, room for k_init_finish's results on m
-// list entries (28 m bytes).
+// list entries (28 m bytes).  These buffers stay valid until the next call of that family on the ctx (track_host.cpp).
 struct TrackInitView {
     const float *kp1, *kp2, *pts;
     const int32_t* lists;
@@ -514,13 +552,5 @@ void ba_launch_stats(int device, long long* launches, long long* windows, double
 void ba_service_times(int device, double* out5);
 void ba_service_park(int device);
 void ba_resident_stats(int device, long long* windows, long long* grid_starts, double* cycles = nullptr, long long* path_switches = nullptr);
-// hipFree / hipHostFree with the resident solver grid of `device` taken off first (both synchronise with every stream of the
-// device; the grid never ends on its own)
-void ba_service_free(int device, void* p, bool host);
-inline void mvo_free_on_current_device(void* p) {
-    int d = 0;
-    (void)hipGetDevice(&d);
-    ba_service_free(d, p, false);
-}
 
 #endif

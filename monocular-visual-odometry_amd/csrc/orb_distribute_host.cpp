@@ -22,12 +22,7 @@ inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 void distribute_release(mvo_ctx* ctx) {
-    mvo_orb_distribute_state* s = ctx->dist;
-    if (!s) return;
-    void* dev[] = {s->d_cells, s->d_disc};
-    for (void* p : dev)
-        if (p) mvo_free_on_current_device(p);
-    delete s;
+    delete ctx->dist;
     ctx->dist = nullptr;
 }
 
@@ -111,16 +106,15 @@ int setup_cells(mvo_ctx* ctx, int w, int h) {
     }
     s->n_records = slot;
     s->kp_cap = kp_cap;
-    if (s->d_cells) mvo_free_on_current_device(s->d_cells);
-    s->d_cells = nullptr;
+    s->d_cells.release();
     if (!s->cells.empty()) {
-        MVO_HIP(hipMalloc((void**)&s->d_cells, s->cells.size() * sizeof(DistCell)));
+        if (int r = s->d_cells.ensure_exact(ctx, s->cells.size())) return r;
         MVO_HIP(hipMemcpy(s->d_cells, s->cells.data(), s->cells.size() * sizeof(DistCell), hipMemcpyHostToDevice));
     }
     if (!s->d_disc) {
         signed char disc[768 * 2] = {0};
         s->disc_n = ic_disc(disc);
-        MVO_HIP(hipMalloc((void**)&s->d_disc, sizeof disc));
+        if (int r = s->d_disc.ensure_exact(ctx, sizeof disc)) return r;
         MVO_HIP(hipMemcpy(s->d_disc, disc, sizeof disc, hipMemcpyHostToDevice));
     }
     s->made_orb = ctx->orb;
@@ -372,15 +366,7 @@ int mvo_calc_keypoints_distributed(mvo_ctx* ctx, const uint8_t* image, int w, in
     int r = check_image(ctx, image, w, h, stride, ch, kps, n);
     if (r) return r;
     MVO_HIP(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)h * stride;
-    if (ctx->d_img_cap < bytes) {  // (the staging buffer mvo_calc_keypoints uploads into)
-        if (ctx->d_img) ba_service_free(ctx->device, ctx->d_img, false);
-        ctx->d_img = nullptr;
-        ctx->d_img_cap = 0;
-        MVO_HIP(hipMalloc((void**)&ctx->d_img, bytes + 64));
-        ctx->d_img_cap = bytes;
-    }
-    MVO_HIP(hipMemcpyAsync(ctx->d_img, image, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = mvo_stage_image(ctx, image, h, stride))) return r;  // (the staging buffer mvo_calc_keypoints uploads into)
     return finish(ctx, ctx->d_img, w, h, stride, ch, kps, cap, n);
 }
 

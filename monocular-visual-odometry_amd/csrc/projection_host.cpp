@@ -15,13 +15,7 @@
 namespace {
 
 void projection_release(mvo_ctx* ctx) {
-    mvo_projection_state* e = ctx->proj;
-    if (!e) return;
-    void* dev[] = {e->d_t, e->d_tg};
-    for (void* p : dev)
-        if (p) mvo_free_on_current_device(p);
-    e->scratch.release();
-    delete e;
+    delete ctx->proj;
     ctx->proj = nullptr;
 }
 
@@ -31,18 +25,10 @@ int ensure_bufs(mvo_ctx* ctx, int n_map, int nt) {
         ctx->proj_release = projection_release;
     }
     mvo_projection_state* e = ctx->proj;
-    if (int r = e->scratch.ensure(ctx, n_map)) return r;
-    if (nt > e->cap_t) {
-        void* old[] = {e->d_t, e->d_tg};
-        for (void* p : old)
-            if (p) mvo_free_on_current_device(p);
-        e->d_t = nullptr, e->d_tg = nullptr;
-        e->cap_t = 0;
-        const size_t cap = (size_t)std::max(4096, nt + nt / 2);
-        MVO_HIP(hipMalloc((void**)&e->d_t, cap * 32));
-        MVO_HIP(hipMalloc((void**)&e->d_tg, cap * 24));
-        e->cap_t = (int)cap;
-    }
+    int r;
+    if ((r = e->scratch.ensure(ctx, n_map)) || (r = e->d_t.ensure(ctx, (size_t)nt * 32, 4096 * 32)) ||
+        (r = e->d_tg.ensure(ctx, (size_t)nt * 3, 4096 * 3)))
+        return r;
     return MVO_OK;
 }
 

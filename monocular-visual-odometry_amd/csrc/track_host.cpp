@@ -11,80 +11,61 @@
 
 struct mvo_track_state {
     // PnP: pairs, subsets, per-hypothesis results, refinement scratch
-    double *d_Mg = nullptr, *d_mg = nullptr;
-    int cap_n = 0;
-    uint8_t* d_in = nullptr;  // pairs + subsets of a solvePnPRansac call, contiguous like their pinned staging (one upload)
-    size_t cap_in = 0;
-    double* d_models = nullptr;
-    int32_t* d_counts = nullptr;
-    int cap_h = 0;
-    uint8_t* d_masks = nullptr;
+    DevBuf<double> d_Mg, d_mg;
+    DevBuf<uint8_t> d_in;  // pairs + subsets of a solvePnPRansac call, contiguous like their pinned staging (one upload)
+    DevBuf<double> d_models;
+    DevBuf<int32_t> d_counts;
+    DevBuf<uint8_t> d_masks;
     int last_loop_len = 0;  // iterations the RANSAC loop of the previous mvo_solve_pnp_ransac on this ctx ran (0: none yet)
-    size_t cap_masks = 0;
     // record of the last solve (mvo_debug_get_pnp)
     std::vector<double> models;
     std::vector<int32_t> counts;
     int32_t info[6] = {-1, 0, 0, 0, 0, 0};
     // triangulation
-    float *d_tri_in = nullptr, *d_tri_out = nullptr;
-    int cap_tri = 0;
+    DevBuf<float> d_tri_in, d_tri_out;
     // essential-matrix RANSAC
-    double* d_emq = nullptr;  // q1 (2n) then q2 (2n)
-    uint8_t* d_em_mask = nullptr;
-    int cap_em = 0;
-    int32_t *d_em_subsets = nullptr, *d_em_nm = nullptr, *d_em_counts = nullptr;
-    double* d_em_E = nullptr;
+    DevBuf<double> d_emq;  // q1 (2n) then q2 (2n)
+    DevBuf<uint8_t> d_em_mask;
+    DevBuf<int32_t> d_em_subsets, d_em_nm, d_em_counts;
+    DevBuf<double> d_em_E;
     std::vector<int32_t> em_counts;  // record of the last call: [iterations evaluated x 10]
     int32_t em_info[5] = {-1, -1, 0, 0, 0};
     // homography RANSAC
-    float* d_hpts = nullptr;  // src (2n) then dst (2n)
-    uint8_t* d_h_mask = nullptr;
-    int cap_h_pts = 0;
-    int32_t *d_h_subsets = nullptr, *d_h_counts = nullptr;
-    double *d_h_H = nullptr, *d_h_out = nullptr;
+    DevBuf<float> d_hpts;  // src (2n) then dst (2n)
+    DevBuf<uint8_t> d_h_mask;
+    DevBuf<int32_t> d_h_subsets, d_h_counts;
+    DevBuf<double> d_h_H, d_h_out;
     std::vector<int32_t> h_counts;  // record of the last call: [iterations evaluated]
     int32_t h_info[6] = {-1, 0, 0, 0, 0, 0};
     // recoverPose after the essential-matrix RANSAC (record of the last call: mvo_debug_get_recover_pose)
-    uint8_t* d_rp_masks = nullptr;
-    int cap_rp = 0;
-    double* d_rp_out = nullptr;
-    int32_t* d_rp_cnt = nullptr;
+    DevBuf<uint8_t> d_rp_masks;
+    DevBuf<double> d_rp_out;
+    DevBuf<int32_t> d_rp_cnt;
     int32_t rp_good[4] = {0, 0, 0, 0};
     int32_t rp_chosen = -1;
     double rp_R1R2t[21] = {};
     std::vector<uint8_t> rp_masks;
     int rp_n = 0;
     // E / H scores
-    uint8_t* d_sc_in = nullptr;  // pts1 (2n float), pts2 (2n float), the E list, the H list
-    size_t cap_sc = 0;
-    int32_t* d_sc_kept = nullptr;
-    size_t cap_sc_kept = 0;
-    uint8_t* d_sc_out = nullptr;  // 2 scores, 2 kept counts
+    DevBuf<uint8_t> d_sc_in;  // pts1 (2n float), pts2 (2n float), the E list, the H list
+    DevBuf<int32_t> d_sc_kept;
+    DevBuf<uint8_t> d_sc_out;  // 2 scores, 2 kept counts
     // homography decomposition (record of the last call: mvo_debug_get_homography_decomposition) and the
     // triangulation of the initialisation's solutions ([5][n] points)
-    double* d_hd_out = nullptr;
-    int32_t* d_hd_cnt = nullptr;
+    DevBuf<double> d_hd_out;
+    DevBuf<int32_t> d_hd_cnt;
     double hd_out[kHdOut] = {};
     int32_t hd_cnt[kHdCnt] = {};
-    float* d_ip_pts = nullptr;
-    size_t cap_ip_pts = 0;
-    uint8_t* d_fin = nullptr;  // k_init_finish's results
-    size_t cap_fin = 0;
+    DevBuf<float> d_ip_pts;
+    DevBuf<uint8_t> d_fin;  // k_init_finish's results
     // map points in view
-    uint8_t* d_view_desc = nullptr;
-    int32_t* d_view_n = nullptr;
-    int cap_view = 0;
+    DevBuf<uint8_t> d_view_desc;
+    DevBuf<int32_t> d_view_n;
 };
 
 int g_pnp_replay_skew = 0;
 
 namespace {
-
-template <class T>
-void free_dev(T*& p) {
-    if (p) mvo_free_on_current_device(p);
-    p = nullptr;
-}
 
 mvo_track_state* state(mvo_ctx* ctx) {
     if (!ctx->track) ctx->track = new mvo_track_state();
@@ -93,40 +74,12 @@ mvo_track_state* state(mvo_ctx* ctx) {
 
 int ensure_pnp(mvo_ctx* ctx, int n, int n_hyp) {
     mvo_track_state* s = state(ctx);
-    if (n > s->cap_n) {
-        free_dev(s->d_Mg);
-        free_dev(s->d_mg);
-        s->cap_n = 0;
-        const int cap = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_Mg, (size_t)cap * 3 * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_mg, (size_t)cap * 2 * sizeof(double)));
-        s->cap_n = cap;
-    }
-    if (n_hyp > s->cap_h) {
-        free_dev(s->d_models);
-        free_dev(s->d_counts);
-        s->cap_h = 0;
-        const int cap = std::max(128, n_hyp);
-        MVO_HIP(hipMalloc((void**)&s->d_models, (size_t)cap * 12 * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_counts, (size_t)cap * sizeof(int32_t)));
-        s->cap_h = cap;
-    }
-    const size_t in_need = (size_t)n * 20 + (size_t)n_hyp * 20 + 64;
-    if (in_need > s->cap_in) {
-        free_dev(s->d_in);
-        s->cap_in = 0;
-        const size_t cap = in_need + in_need / 2 + 4096;
-        MVO_HIP(hipMalloc((void**)&s->d_in, cap));
-        s->cap_in = cap;
-    }
-    const size_t need = (size_t)n_hyp * (size_t)n;
-    if (need > s->cap_masks) {
-        free_dev(s->d_masks);
-        s->cap_masks = 0;
-        const size_t cap = std::max<size_t>(need + need / 2, (size_t)1 << 20);
-        MVO_HIP(hipMalloc((void**)&s->d_masks, cap));
-        s->cap_masks = cap;
-    }
+    const size_t N = n, H = n_hyp;
+    int r;
+    if ((r = s->d_Mg.ensure(ctx, N * 3, 4096 * 3)) || (r = s->d_mg.ensure(ctx, N * 2, 4096 * 2)) ||
+        (r = s->d_models.ensure(ctx, H * 12, 128 * 12)) || (r = s->d_counts.ensure(ctx, H, 128)) ||
+        (r = s->d_in.ensure(ctx, N * 20 + H * 20 + 64, 4096)) || (r = s->d_masks.ensure(ctx, H * N, (size_t)1 << 20)))
+        return r;
     return MVO_OK;
 }
 
@@ -261,19 +214,40 @@ int draw_h_subsets(const float* src, const float* dst, int count, int max_iters,
     return max_iters;
 }
 
-// The sequential bookkeeping of RANSACPointSetRegistrator::run over device-evaluated hypotheses, shared by
-// findEssentialMat and findHomography.  The hypotheses [0, total) are launched in two chunks (chunk_end); after each
-// chunk the counts (per_hyp candidates per hypothesis, -1 = none) are read back and the loop is advanced until its own
-// adaptive stopping rule (RANSACUpdateNumIters, starting from niters) is met.  count == model_points: the first
-// model is the answer.  rec receives every evaluated count; info = {best hypothesis, best candidate, iterations the
+// The sequential loop of RANSACPointSetRegistrator::run over counts that exist so far: which model is the best and how many
+// iterations the loop's own adaptive stopping rule (RANSACUpdateNumIters, starting from niters) still wants.
+struct RansacLoop {
+    int niters, max_good = 0, it = 0, best_it = -1, best_m = -1;
+    // counts: per_hyp candidates per hypothesis (-1 = none) of the hypotheses [0, evaluated)
+    void advance(const int32_t* counts, int evaluated, int per_hyp, int n, int model_points, double prob) {
+        for (; it < niters && it < evaluated; ++it)
+            for (int m = 0; m < per_hyp; ++m) {
+                const int raw = counts[(size_t)it * per_hyp + m];
+                const int good = n == model_points && raw >= 0 ? n : raw;
+                if (good < 0) break;
+                if (good > std::max(max_good, model_points - 1)) {
+                    max_good = good;
+                    best_it = it;
+                    best_m = m;
+                    niters = update_num_iters(prob, (double)(n - good) / n, model_points, niters);
+                }
+                if (n == model_points) break;  // count == modelPoints: the first model is the answer
+            }
+    }
+};
+
+// RansacLoop over device-evaluated hypotheses, shared by findEssentialMat and findHomography.  The hypotheses [0, total)
+// are launched in two chunks (chunk_end); after each chunk the counts are read back and the loop is advanced until its
+// own stopping rule is met.  rec receives every evaluated count; info = {best hypothesis, best candidate, iterations the
 // sequential loop ran, hypotheses evaluated}.  The pinned staging may hold this call's uploads on entry.
 template <class Launch>
 int ransac_chunks(mvo_ctx* ctx, int n, int model_points, int total, int niters, int per_hyp, double prob,
                   const int (&chunk_end)[2], const int32_t* d_counts, Launch&& launch, std::vector<int32_t>& rec,
                   int32_t* info) {
-    int evaluated = 0, max_good = 0, it = 0, best_it = -1, best_m = -1, r;
+    int evaluated = 0, r;
+    RansacLoop loop{niters};
     bool first_wait = true;
-    for (int c = 0; c < 2 && it < niters; ++c) {
+    for (int c = 0; c < 2 && loop.it < loop.niters; ++c) {
         const int end = std::min(chunk_end[c], total);
         if (end <= evaluated) continue;
         if ((r = launch(evaluated, end))) return r;
@@ -287,23 +261,11 @@ int ransac_chunks(mvo_ctx* ctx, int n, int model_points, int total, int niters, 
         MVO_HIP(hipStreamSynchronize(ctx->stream));
         rec.insert(rec.end(), h_counts, h_counts + (size_t)(end - evaluated) * per_hyp);
         evaluated = end;
-        for (; it < niters && it < evaluated; ++it)
-            for (int m = 0; m < per_hyp; ++m) {
-                const int raw = rec[(size_t)it * per_hyp + m];
-                const int good = n == model_points && raw >= 0 ? n : raw;
-                if (good < 0) break;
-                if (good > std::max(max_good, model_points - 1)) {
-                    max_good = good;
-                    best_it = it;
-                    best_m = m;
-                    niters = update_num_iters(prob, (double)(n - good) / n, model_points, niters);
-                }
-                if (n == model_points) break;  // count == modelPoints: the first model is the answer
-            }
+        loop.advance(rec.data(), evaluated, per_hyp, n, model_points, prob);
     }
-    info[0] = best_it;
-    info[1] = best_m;
-    info[2] = it;
+    info[0] = loop.best_it;
+    info[1] = loop.best_m;
+    info[2] = loop.it;
     info[3] = evaluated;
     return MVO_OK;
 }
@@ -325,28 +287,17 @@ int essential_ransac(mvo_ctx* ctx, const float* kp_prev, const float* kp_curr, i
     constexpr int kModel = 5, kMaxIters = 1000;  // createRANSACPointSetRegistrator(cb, 5, threshold, prob) -> maxIters 1000
     if (n < kModel) return MVO_OK;
     MVO_HIP(hipSetDevice(ctx->device));
-    if (n > s->cap_em) {
-        free_dev(s->d_emq);
-        free_dev(s->d_em_mask);
-        s->cap_em = 0;
-        const int c = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_emq, (size_t)c * 4 * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_mask, (size_t)c));
-        s->cap_em = c;
-    }
-    if (!s->d_em_subsets) {
-        MVO_HIP(hipMalloc((void**)&s->d_em_subsets, (size_t)kMaxIters * 5 * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_nm, (size_t)kMaxIters * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_counts, (size_t)kMaxIters * 10 * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_em_E, (size_t)kMaxIters * 90 * sizeof(double)));
-    }
+    int r;
+    if ((r = s->d_emq.ensure(ctx, (size_t)n * 4, 4096 * 4)) || (r = s->d_em_mask.ensure(ctx, n, 4096)) ||
+        (r = s->d_em_subsets.ensure_exact(ctx, kMaxIters * 5)) || (r = s->d_em_nm.ensure_exact(ctx, kMaxIters)) ||
+        (r = s->d_em_counts.ensure_exact(ctx, kMaxIters * 10)) || (r = s->d_em_E.ensure_exact(ctx, kMaxIters * 90)))
+        return r;
     // findEssentialMat(points1, points2, focal, pp, ...): K = [focal 0 pp.x; 0 focal pp.y], pp a cv::Point2f built from
     // K(0,2), K(1,2) (epipolar_geometry.cpp:27-28); points to double, (p - c) / f; threshold /= (fx + fy) / 2
     const double focal = (fx + fy) / 2;
     const double pcx = (double)(float)cx, pcy = (double)(float)cy;
     const size_t bq = (size_t)n * 4 * sizeof(double), bs = (size_t)kMaxIters * 5 * sizeof(int32_t);
-    int r = mvo_ensure_pinned(ctx, std::max(bq + bs, (size_t)kMaxIters * 40 + 2 * (size_t)n + 512));
-    if (r) return r;
+    if ((r = mvo_ensure_pinned(ctx, std::max(bq + bs, (size_t)kMaxIters * 40 + 2 * (size_t)n + 512)))) return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));
     double* q = reinterpret_cast<double*>(ctx->h_pin);
     for (int i = 0; i < n; ++i) {
@@ -416,25 +367,14 @@ void mul3(const double* A, const double* B, double* C) {
 
 int ensure_tri(mvo_ctx* ctx, int n) {
     mvo_track_state* s = state(ctx);
-    if (n > s->cap_tri) {
-        free_dev(s->d_tri_in);
-        free_dev(s->d_tri_out);
-        s->cap_tri = 0;
-        const int cap = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_tri_in, (size_t)cap * 4 * sizeof(float)));
-        MVO_HIP(hipMalloc((void**)&s->d_tri_out, (size_t)cap * 6 * sizeof(float)));
-        s->cap_tri = cap;
-    }
-    return MVO_OK;
+    if (int r = s->d_tri_in.ensure(ctx, (size_t)n * 4, 4096 * 4)) return r;
+    return s->d_tri_out.ensure(ctx, (size_t)n * 6, 4096 * 6);
 }
 
 int ensure_hd(mvo_ctx* ctx) {
     mvo_track_state* s = state(ctx);
-    if (!s->d_hd_out) {
-        MVO_HIP(hipMalloc((void**)&s->d_hd_out, kHdOut * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_hd_cnt, kHdCnt * sizeof(int32_t)));
-    }
-    return MVO_OK;
+    if (int r = s->d_hd_out.ensure_exact(ctx, kHdOut)) return r;
+    return s->d_hd_cnt.ensure_exact(ctx, kHdCnt);
 }
 
 void reset_hd_record(mvo_track_state* s) {
@@ -443,8 +383,8 @@ void reset_hd_record(mvo_track_state* s) {
 }
 
 // The H that mvo_find_homography left on the device (found == 1) and its RANSAC mask (NULL: all four matches)
-const double* device_h(const mvo_track_state* s, int n) { return n == 4 ? s->d_h_H + 9 * (size_t)s->h_info[0] : s->d_h_out; }
-const uint8_t* device_h_mask(const mvo_track_state* s, int n) { return n == 4 ? nullptr : s->d_h_mask; }
+const double* device_h(const mvo_track_state* s, int n) { return n == 4 ? s->d_h_H + 9 * (size_t)s->h_info[0] : s->d_h_out.p; }
+const uint8_t* device_h_mask(const mvo_track_state* s, int n) { return n == 4 ? nullptr : s->d_h_mask.p; }
 
 // basics::invRt: [R t; 0 1].inv() by the LU of mvo_invert_pose (cv::Mat::inv leaves zeros for a singular matrix)
 void inv_rt(double* R, double* t) {
@@ -460,56 +400,18 @@ void inv_rt(double* R, double* t) {
 }  // namespace
 
 void track_release(mvo_ctx* ctx) {
-    mvo_track_state* s = ctx->track;
-    if (!s) return;
-    free_dev(s->d_Mg);
-    free_dev(s->d_mg);
-    free_dev(s->d_in);
-    free_dev(s->d_models);
-    free_dev(s->d_counts);
-    free_dev(s->d_masks);
-    free_dev(s->d_view_desc);
-    free_dev(s->d_view_n);
-    free_dev(s->d_tri_in);
-    free_dev(s->d_tri_out);
-    free_dev(s->d_emq);
-    free_dev(s->d_em_mask);
-    free_dev(s->d_em_subsets);
-    free_dev(s->d_em_nm);
-    free_dev(s->d_em_counts);
-    free_dev(s->d_em_E);
-    free_dev(s->d_hpts);
-    free_dev(s->d_h_mask);
-    free_dev(s->d_h_subsets);
-    free_dev(s->d_h_counts);
-    free_dev(s->d_h_H);
-    free_dev(s->d_h_out);
-    free_dev(s->d_rp_masks);
-    free_dev(s->d_rp_out);
-    free_dev(s->d_rp_cnt);
-    free_dev(s->d_sc_in);
-    free_dev(s->d_sc_kept);
-    free_dev(s->d_sc_out);
-    free_dev(s->d_hd_out);
-    free_dev(s->d_hd_cnt);
-    free_dev(s->d_ip_pts);
-    free_dev(s->d_fin);
-    delete s;
+    delete ctx->track;
     ctx->track = nullptr;
 }
 
+// The initialisation's lifetime rule: what mvo_estimate_possible_relative_poses leaves on the device (d_sc_in, d_ip_pts,
+// d_rp_out, d_hd_out, d_em_mask and the d_h_* buffers) stays valid until the next call of that family on the ctx; only such
+// a call may regrow them.  The view hands those pointers out and grows nothing but d_fin.
 int track_init_view(mvo_ctx* ctx, int n, int m, TrackInitView* v) {
     mvo_track_state* s = state(ctx);
-    const size_t bytes = (size_t)m * 28;
-    if (bytes > s->cap_fin) {
-        free_dev(s->d_fin);
-        s->cap_fin = 0;
-        const size_t c = std::max<size_t>(1 << 16, bytes + bytes / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_fin, c));
-        s->cap_fin = c;
-    }
+    if (int r = s->d_fin.ensure(ctx, (size_t)m * 28, 1 << 16)) return r;
     v->out = s->d_fin;
-    v->kp1 = reinterpret_cast<const float*>(s->d_sc_in);
+    v->kp1 = reinterpret_cast<const float*>(s->d_sc_in.p);
     v->kp2 = reinterpret_cast<const float*>(s->d_sc_in + (size_t)n * 8);
     v->lists = reinterpret_cast<const int32_t*>(s->d_sc_in + (size_t)n * 16);
     v->pts = s->d_ip_pts;
@@ -533,8 +435,6 @@ void mvo_map_release(mvo_ctx* ctx, mvo_map* map) {
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
     }
-    free_dev(map->d_pos);
-    free_dev(map->d_desc);
     delete map;
 }
 
@@ -542,21 +442,14 @@ int mvo_map_upload(mvo_ctx* ctx, mvo_map* map, const float* pos, const uint8_t* 
     if (!ctx || !map || n < 0 || (n && (!pos || !desc)))
         return mvo_set_err(ctx, MVO_ERR_INVALID, "bad arguments", hipSuccess);
     MVO_HIP(hipSetDevice(ctx->device));
-    if (n > map->cap) {
-        MVO_HIP(hipStreamSynchronize(ctx->stream));
-        free_dev(map->d_pos);
-        free_dev(map->d_desc);
-        map->cap = 0;
-        const int cap = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&map->d_pos, (size_t)cap * 3 * sizeof(float)));
-        MVO_HIP(hipMalloc((void**)&map->d_desc, (size_t)cap * 32));
-        map->cap = cap;
-    }
+    const size_t n_pos = (size_t)n * 3, n_desc = (size_t)n * 32;
+    int r;
+    if (n_pos > map->d_pos.cap || n_desc > map->d_desc.cap) MVO_HIP(hipStreamSynchronize(ctx->stream));
+    if ((r = map->d_pos.ensure(ctx, n_pos, 4096 * 3)) || (r = map->d_desc.ensure(ctx, n_desc, 4096 * 32))) return r;
     map->n = n;
     if (n) {
         // staged through pinned memory so that the caller's arrays may be reused as soon as we return
-        int r = mvo_ensure_pinned(ctx, (size_t)n * 44);
-        if (r) return r;
+        if ((r = mvo_ensure_pinned(ctx, (size_t)n * 44))) return r;
         MVO_HIP(hipStreamSynchronize(ctx->stream));
         std::memcpy(ctx->h_pin, pos, (size_t)n * 12);
         std::memcpy(ctx->h_pin + (size_t)n * 12, desc, (size_t)n * 32);
@@ -600,18 +493,11 @@ int mvo_map_points_in_view(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, doub
     if (map->n == 0) return MVO_OK;
     MVO_HIP(hipSetDevice(ctx->device));
     mvo_track_state* s = state(ctx);
-    if (map->n > s->cap_view) {
-        free_dev(s->d_view_desc);
-        s->cap_view = 0;
-        const int c = std::max(4096, map->n + map->n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_view_desc, (size_t)c * 32));
-        s->cap_view = c;
-    }
-    if (!s->d_view_n) MVO_HIP(hipMalloc((void**)&s->d_view_n, 4));
+    int r;
+    if ((r = s->d_view_desc.ensure(ctx, (size_t)map->n * 32, 4096 * 32)) || (r = s->d_view_n.ensure_exact(ctx, 1))) return r;
     // the kernel writes the count, the indices and the pixels straight into the pinned buffer (the descriptors of the survivors
     // stay in HBM for the matcher): one synchronisation, no copy
-    int r = mvo_ensure_pinned(ctx, 192 + (size_t)map->n * 12);
-    if (r) return r;
+    if ((r = mvo_ensure_pinned(ctx, 192 + (size_t)map->n * 12))) return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
     int32_t* h_n = reinterpret_cast<int32_t*>(ctx->h_pin);
     int32_t* h_idx = reinterpret_cast<int32_t*>(ctx->h_pin + 64);
@@ -669,7 +555,7 @@ int mvo_solve_pnp_ransac(mvo_ctx* ctx, const float* pts3d, const float* pts2d, i
     else
         draw_subsets(n, n_hyp, subsets);
     MVO_HIP(hipMemcpyAsync(s->d_in, ctx->h_pin, b3 + b2 + bs, hipMemcpyHostToDevice, ctx->stream));
-    const float* d_p3 = reinterpret_cast<const float*>(s->d_in);
+    const float* d_p3 = reinterpret_cast<const float*>(s->d_in.p);
     const float* d_p2 = reinterpret_cast<const float*>(s->d_in + b3);
     const int32_t* d_subsets = reinterpret_cast<const int32_t*>(s->d_in + b3 + b2);
     uint8_t* h_out = ctx->h_pin + o_out;
@@ -715,18 +601,10 @@ int mvo_solve_pnp_ransac(mvo_ctx* ctx, const float* pts3d, const float* pts2d, i
         s->info[1] = 1;
     } else {
         // the loop's bookkeeping with its own bound (n_hyp), over the counts that exist so far
-        const int32_t* cnts = reinterpret_cast<const int32_t*>(h_counts);
-        int niters = n_hyp, max_good = 0, it = 0;
+        RansacLoop loop{n_hyp};
         for (;;) {
-            for (; it < niters && it < evaluated; ++it) {
-                const int good = cnts[it];
-                if (good > std::max(max_good, kModel - 1)) {
-                    max_good = good;
-                    best = it;
-                    niters = update_num_iters(confidence, (double)(n - good) / n, kModel, niters);
-                }
-            }
-            if (it >= niters || evaluated >= n_hyp) break;
+            loop.advance(reinterpret_cast<const int32_t*>(h_counts), evaluated, 1, n, kModel, confidence);
+            if (loop.it >= loop.niters || evaluated >= n_hyp) break;
             // the sequential loop goes on behind the first chunk: the remaining hypotheses, then the refinement over all counts
             if ((r = track_launch_pnp_hypotheses(ctx, d_p3, d_p2, n, d_subsets + (size_t)kModel * evaluated, n_hyp - evaluated, cam, thr2,
                                                  s->d_models + 12 * (size_t)evaluated, s->d_counts + evaluated, s->d_masks + (size_t)evaluated * n,
@@ -739,8 +617,8 @@ int mvo_solve_pnp_ransac(mvo_ctx* ctx, const float* pts3d, const float* pts2d, i
             if ((r = fetch())) return r;
             evaluated = n_hyp;
         }
-        s->info[1] = it;
-        s->last_loop_len = it;
+        best = loop.best_it;
+        s->info[1] = s->last_loop_len = loop.it;
     }
     s->counts.assign(reinterpret_cast<int32_t*>(h_counts), reinterpret_cast<int32_t*>(h_counts) + evaluated);
     s->models.resize((size_t)evaluated * 12);
@@ -874,17 +752,8 @@ int mvo_esti_motion_by_essential(mvo_ctx* ctx, const float* pts1, const float* p
         if (ctx->prof) mvo_prof_collect(ctx);
         return MVO_OK;
     }
-    if (n > s->cap_rp) {
-        free_dev(s->d_rp_masks);
-        s->cap_rp = 0;
-        const int c = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_rp_masks, (size_t)c));
-        s->cap_rp = c;
-    }
-    if (!s->d_rp_out) {
-        MVO_HIP(hipMalloc((void**)&s->d_rp_out, 48 * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_rp_cnt, 8 * sizeof(int32_t)));
-    }
+    if ((r = s->d_rp_masks.ensure(ctx, n, 4096)) || (r = s->d_rp_out.ensure_exact(ctx, 48)) || (r = s->d_rp_cnt.ensure_exact(ctx, 8)))
+        return r;
     const double* d_q1 = s->d_emq;
     const double* d_q2 = s->d_emq + 2 * (size_t)n;
     if ((r = track_launch_recover_pose(ctx, d_q1, d_q2, n, s->d_em_E + 90 * (size_t)best_it + 9 * (size_t)best_m,
@@ -967,34 +836,22 @@ int mvo_check_init_scores(mvo_ctx* ctx, const float* pts1, const float* pts2, in
     MVO_HIP(hipSetDevice(ctx->device));
     mvo_track_state* s = state(ctx);
     const size_t bp = (size_t)n * 16, bl = (size_t)(me + mh) * 4;
-    if (bp + bl > s->cap_sc) {
-        free_dev(s->d_sc_in);
-        s->cap_sc = 0;
-        const size_t c = std::max<size_t>(1 << 16, bp + bl + (bp + bl) / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_sc_in, c));
-        s->cap_sc = c;
-    }
-    if ((size_t)(me + mh) > s->cap_sc_kept) {
-        free_dev(s->d_sc_kept);
-        s->cap_sc_kept = 0;
-        const size_t c = std::max<size_t>(4096, (size_t)(me + mh) * 3 / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_sc_kept, c * 4));
-        s->cap_sc_kept = c;
-    }
-    if (!s->d_sc_out) MVO_HIP(hipMalloc((void**)&s->d_sc_out, 64));
+    int r;
+    if ((r = s->d_sc_in.ensure(ctx, bp + bl, 1 << 16)) || (r = s->d_sc_kept.ensure(ctx, me + mh, 4096)) ||
+        (r = s->d_sc_out.ensure_exact(ctx, 64)))
+        return r;
     const size_t o_out = (bp + bl + 63) / 64 * 64;
-    int r = mvo_ensure_pinned(ctx, o_out + 64 + (size_t)(me + mh) * 4);
-    if (r) return r;
+    if ((r = mvo_ensure_pinned(ctx, o_out + 64 + (size_t)(me + mh) * 4))) return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));
     std::memcpy(ctx->h_pin, pts1, (size_t)n * 8);
     std::memcpy(ctx->h_pin + (size_t)n * 8, pts2, (size_t)n * 8);
     if (me) std::memcpy(ctx->h_pin + bp, inl_e, (size_t)me * 4);
     if (mh) std::memcpy(ctx->h_pin + bp + (size_t)me * 4, inl_h, (size_t)mh * 4);
     MVO_HIP(hipMemcpyAsync(s->d_sc_in, ctx->h_pin, bp + bl, hipMemcpyHostToDevice, ctx->stream));
-    const float* d_p1 = reinterpret_cast<const float*>(s->d_sc_in);
+    const float* d_p1 = reinterpret_cast<const float*>(s->d_sc_in.p);
     const float* d_p2 = reinterpret_cast<const float*>(s->d_sc_in + (size_t)n * 8);
     const int32_t* d_lists = reinterpret_cast<const int32_t*>(s->d_sc_in + bp);
-    double* d_scores = reinterpret_cast<double*>(s->d_sc_out);
+    double* d_scores = reinterpret_cast<double*>(s->d_sc_out.p);
     int32_t* d_nk = reinterpret_cast<int32_t*>(s->d_sc_out + 16);
     if ((r = track_launch_init_scores(ctx, d_p1, d_p2, d_lists, me, mh, a, d_scores, s->d_sc_kept, d_nk))) return r;
     uint8_t* h_out = ctx->h_pin + o_out;
@@ -1047,24 +904,13 @@ int mvo_find_homography(mvo_ctx* ctx, const float* src, const float* dst, int n,
     if (cap < n) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_find_homography: inlier buffer smaller than n", hipSuccess);
     if (threshold <= 0) threshold = 3;  // findHomography's defaultRANSACReprojThreshold
     MVO_HIP(hipSetDevice(ctx->device));
-    if (n > s->cap_h_pts) {
-        free_dev(s->d_hpts);
-        free_dev(s->d_h_mask);
-        s->cap_h_pts = 0;
-        const int c = std::max(4096, n + n / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_hpts, (size_t)c * 4 * sizeof(float)));
-        MVO_HIP(hipMalloc((void**)&s->d_h_mask, (size_t)c));
-        s->cap_h_pts = c;
-    }
-    if (!s->d_h_subsets) {
-        MVO_HIP(hipMalloc((void**)&s->d_h_subsets, (size_t)kMaxIters * 4 * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_h_counts, (size_t)kMaxIters * sizeof(int32_t)));
-        MVO_HIP(hipMalloc((void**)&s->d_h_H, (size_t)kMaxIters * 9 * sizeof(double)));
-        MVO_HIP(hipMalloc((void**)&s->d_h_out, 16 * sizeof(double)));
-    }
+    int r;
+    if ((r = s->d_hpts.ensure(ctx, (size_t)n * 4, 4096 * 4)) || (r = s->d_h_mask.ensure(ctx, n, 4096)) ||
+        (r = s->d_h_subsets.ensure_exact(ctx, kMaxIters * 4)) || (r = s->d_h_counts.ensure_exact(ctx, kMaxIters)) ||
+        (r = s->d_h_H.ensure_exact(ctx, kMaxIters * 9)) || (r = s->d_h_out.ensure_exact(ctx, 16)))
+        return r;
     const size_t bp = (size_t)n * 16, bs = (size_t)kMaxIters * 4 * sizeof(int32_t);
-    int r = mvo_ensure_pinned(ctx, std::max(bp + bs, (size_t)kMaxIters * 4 + (size_t)n + 256));
-    if (r) return r;
+    if ((r = mvo_ensure_pinned(ctx, std::max(bp + bs, (size_t)kMaxIters * 4 + (size_t)n + 256)))) return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));
     std::memcpy(ctx->h_pin, src, (size_t)n * 8);
     std::memcpy(ctx->h_pin + (size_t)n * 8, dst, (size_t)n * 8);
@@ -1234,13 +1080,7 @@ int mvo_estimate_possible_relative_poses(mvo_ctx* ctx, const float* pts1, const 
     }
     if ((r = ensure_tri(ctx, n)) || (r = ensure_hd(ctx))) return r;
     const size_t n_pts = (size_t)5 * n * 3;
-    if (n_pts > s->cap_ip_pts) {
-        free_dev(s->d_ip_pts);
-        s->cap_ip_pts = 0;
-        const size_t c = std::max<size_t>(1 << 16, n_pts + n_pts / 2);
-        MVO_HIP(hipMalloc((void**)&s->d_ip_pts, c * sizeof(float)));
-        s->cap_ip_pts = c;
-    }
+    if ((r = s->d_ip_pts.ensure(ctx, n_pts, 1 << 16))) return r;
     const size_t o_out = ((size_t)n * 16 + 63) / 64 * 64, o_pts = o_out + 1024;  // out (744 B), cnt (48 B), points
     if ((r = mvo_ensure_pinned(ctx, o_pts + n_pts * sizeof(float)))) return r;
     MVO_HIP(hipStreamSynchronize(ctx->stream));

@@ -14,12 +14,7 @@ const int kMaxWidth = 8192;            // as the extraction (FT_ROW_TILES)
 const long long kMaxPixels = 1 << 30;  // pixel indices are 32-bit in the kernels, the debug getter counts in int
 
 void undistort_release(mvo_ctx* ctx) {
-    mvo_undistort_state* u = ctx->undist;
-    if (!u) return;
-    void* dev[] = {u->d_map, u->d_src, u->d_dst};
-    for (void* p : dev)
-        if (p) mvo_free_on_current_device(p);
-    delete u;
+    delete ctx->undist;
     ctx->undist = nullptr;
 }
 
@@ -36,16 +31,6 @@ bool normalise(const mvo_undistort_params& in, mvo_undistort_params* out) {
     for (double v : out->coeffs)
         if (!std::isfinite(v)) return false;
     return in.fx != 0 && in.fy != 0;
-}
-
-int grow(mvo_ctx* ctx, void** p, size_t* cap, size_t need, size_t elem) {
-    if (*cap >= need) return MVO_OK;
-    if (*p) mvo_free_on_current_device(*p);
-    *p = nullptr;
-    *cap = 0;
-    MVO_HIP(hipMalloc(p, need * elem + 64));
-    *cap = need;
-    return MVO_OK;
 }
 
 int check_call(mvo_ctx* ctx, const void* img, int w, int h, int stride, int ch, const void* out, int out_stride) {
@@ -82,7 +67,7 @@ int mvo_undistort_configure(mvo_ctx* ctx, const mvo_undistort_params* params, in
     mvo_undistort_state* u = ctx->undist;
     if (u->configured && u->w == width && u->h == height && !std::memcmp(&u->params, &p, sizeof p)) return MVO_OK;
     u->configured = false;
-    int r = grow(ctx, (void**)&u->d_map, &u->map_cap, (size_t)width * height, sizeof(UndistortRec));
+    int r = u->d_map.ensure_exact(ctx, (size_t)width * height, 64);
     if (r) return r;
     const double* k = p.coeffs;
     const UndistortArgs a{p.fx, p.fy, p.cx, p.cy, 1.0 / p.fx, 1.0 / p.fy, k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7]};
@@ -112,8 +97,8 @@ int mvo_undistort(mvo_ctx* ctx, const uint8_t* image, int w, int h, int stride, 
     MVO_HIP(hipSetDevice(ctx->device));
     mvo_undistort_state* u = ctx->undist;
     const size_t in_bytes = extent(w, h, stride, ch), row = (size_t)w * ch;
-    if ((r = grow(ctx, (void**)&u->d_src, &u->src_cap, in_bytes, 1))) return r;
-    if ((r = grow(ctx, (void**)&u->d_dst, &u->dst_cap, row * h, 1))) return r;
+    if ((r = u->d_src.ensure_exact(ctx, in_bytes, 64))) return r;
+    if ((r = u->d_dst.ensure_exact(ctx, row * h, 64))) return r;
     MVO_HIP(hipMemcpyAsync(u->d_src, image, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     if ((r = undistort_launch_remap(ctx, u->d_map, u->d_src, w, h, stride, ch, u->d_dst, (int)row))) return r;
     // the device image is packed; the caller's padding between rows is never written

@@ -235,14 +235,15 @@ def test_the_largest_train_set(mvo, ctx):
 
 
 def test_partial_scratch_regrows_between_calls(mvo):
-    """One context of its own, three raw calls: 64 x 300 (two train groups, so the arrival counters are used), 4200 x 300
-    (past the 4096 floor: the partial scratch is freed, reallocated and its counters zeroed again), 64 x 300 again."""
+    """One context of its own, six raw calls: 64 x 300 (two train groups, so the arrival counters are used), 4200 x 300
+    (past the 4096 floor: the partial scratch and the query staging are freed and reallocated for 6300, the counters zeroed
+    again), 6400 x 300 (past 6300: once more), 64 x 4200 and 64 x 6400 (the train staging the same way), 64 x 300 again."""
     c = mvo.Context(0)
     try:
-        for nq in (64, 4200, 64):
-            q, qxy, t, txy, F, px, scale, want = raw_inputs(mvo, nq, 300, "perturbed", True)
-            assert 0 < want[2].sum() < nq * 300
-            assert_raw_equal(c.match_knn2_epipolar(q, qxy, t, txy, F, px, scale), want, "%d x 300" % nq)
+        for nq, nt in ((64, 300), (4200, 300), (6400, 300), (64, 4200), (64, 6400), (64, 300)):
+            q, qxy, t, txy, F, px, scale, want = raw_inputs(mvo, nq, nt, "perturbed", True)
+            assert 0 < want[2].sum() < nq * nt
+            assert_raw_equal(c.match_knn2_epipolar(q, qxy, t, txy, F, px, scale), want, "%d x %d" % (nq, nt))
     finally:
         c.close()
 

@@ -215,15 +215,16 @@ def test_the_largest_train_set(ctx):
 
 
 def test_partial_scratch_regrows_between_calls(mvo):
-    """One context of its own, three raw calls: 64 x 300 (two train groups, so the arrival counters are used), 4200 x 300
-    (past the 4096 floor: the partial scratch is freed, reallocated and its counters zeroed again), 64 x 300 again."""
+    """One context of its own, six raw calls: 64 x 300 (two train groups, so the arrival counters are used), 4200 x 300
+    (past the 4096 floor: the partial scratch is freed and reallocated for 6300, its counters zeroed again), 6400 x 300 (past
+    6300: once more), 64 x 4200 and 64 x 6400 (the keypoint staging the same way), 64 x 300 again."""
     c = mvo.Context(0)
     try:
-        for n_map in (64, 4200, 64):
-            pos, desc, T, t, txy, r, scale, want = raw_inputs(mvo, n_map, 300, "perturbed", True)
+        for n_map, nt in ((64, 300), (4200, 300), (6400, 300), (64, 4200), (64, 6400), (64, 300)):
+            pos, desc, T, t, txy, r, scale, want = raw_inputs(mvo, n_map, nt, "perturbed", True)
             assert (want[3] > 0).any() and (want[3] == -1).any()
             with resident(c, pos, desc) as m:
-                assert_raw_equal(c.map_match_knn2_projection(m, T, P.FR1_K, COLS, ROWS, t, txy, r, scale), want, "%d x 300" % n_map)
+                assert_raw_equal(c.map_match_knn2_projection(m, T, P.FR1_K, COLS, ROWS, t, txy, r, scale), want, "%d x %d" % (n_map, nt))
     finally:
         c.close()
 

@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import test_gpu_init_finish as T
+import test_gpu_regrow as T_regrow
 from conftest import ROOT
 
 SIM_DIR = os.path.join(ROOT, "tests", "sim")
@@ -61,6 +62,10 @@ def test_four_matches_on_the_emulated_build(simctx, F, O):
 @pytest.mark.parametrize("kind,n,seed,frac,h_slot", T.SCENE_CASES)
 def test_init_two_view_on_the_emulated_build(simctx, F, O, kind, n, seed, frac, h_slot):
     T.test_init_two_view_matches_the_restatement(simctx, F, O, kind, n, seed, frac, h_slot)
+
+
+def test_initialisation_buffers_regrow_on_the_emulated_build(mvo, simctx, F, O):
+    T_regrow.init_chain_steps(mvo, F, O)  # (simctx has pointed the package at the emulated build)
 
 
 def test_parameters_boundary_and_no_solution_on_the_emulated_build(simctx, F, O):

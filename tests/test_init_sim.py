@@ -5,6 +5,7 @@ import pytest
 
 import h_restate as HR
 import test_gpu_init as T_init
+import test_gpu_regrow as T_regrow
 from test_kernels_sim import simctx, simlib, simmvo  # noqa: F401  (fixtures)
 
 
@@ -20,6 +21,10 @@ def test_find_homography_on_the_emulated_build(simctx, R, n, seed, kw):
 
 def test_degenerate_inputs_on_the_emulated_build(simctx, R):
     T_init.degenerate_cases(simctx, R)
+
+
+def test_homography_buffers_regrow_on_the_emulated_build(simmvo, R):
+    T_regrow.homography_steps(simmvo, R)
 
 
 def test_outlier_heavy_input_on_the_emulated_build(simctx, R):

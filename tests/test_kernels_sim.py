@@ -17,6 +17,7 @@ from conftest import ROOT
 import test_gpu_keyframe as T_kf
 import test_gpu_match as T_match
 import test_gpu_orb as T_orb
+import test_gpu_regrow as T_regrow
 import test_gpu_track as T_track
 
 SIM_DIR = os.path.join(ROOT, "tests", "sim")
@@ -145,6 +146,23 @@ def test_triangulation_and_essential_matrix(simmvo, O, simctx):
 
 def test_keyframe_insertion(simmvo, O, simctx):
     T_kf.test_keyframe_insertion_end_to_end(simmvo, O, simctx)
+
+
+# ------------------------------------------------------------------------------------------------ buffers that grow on demand
+def test_triangulation_buffers_regrow(simmvo, O):
+    T_regrow.triangulate_steps(simmvo, O)
+
+
+def test_essential_buffers_regrow(simmvo, O):
+    T_regrow.essential_steps(simmvo, O)
+
+
+def test_resident_map_and_view_buffers_regrow(simmvo, O):
+    T_regrow.map_steps(simmvo, O)
+
+
+def test_pnp_buffers_regrow(simmvo, O):
+    T_regrow.pnp_steps(simmvo, O)
 
 
 # ------------------------------------------------------------------------------------------------ the whole hot path, several callers
