@@ -448,6 +448,45 @@ int mvo_map_refresh(mvo_ctx* ctx, mvo_map* map, const uint8_t* obs_desc /* n_obs
 /* include/my_slam/vo/map.h:19 (map_points_: MapPoint::pos_, descriptor_ of the resident copy).  The resident arrays, for
  * tests: pos n x 3 f32, desc n x 32 (either may be NULL); *n = mvo_map_size; MVO_ERR_CAPACITY (with *n set) if cap < *n. */
 int mvo_debug_get_map(mvo_ctx* ctx, mvo_map* map, float* pos, uint8_t* desc, int cap, int* n);
+/* ---- map point positions refined from all their observations ----------------------------------- */
+/* The reference sets a map point's position once, from two views (pushCurrPointsToMap_, vo.cpp:528-576), and runs its bundle
+ * adjustment with the points fixed (config.yaml:123, is_ba_fix_map_points: "true"): the BA moves poses against these positions
+ * and nothing corrects them.  This is the other half of that alternation: the poses fixed, every point an independent
+ * 3-unknown least-squares problem over all its observations (ORB-SLAM's local mapping, g2o's structure-only solver).
+ * Declared operation by operation in DESIGN.md section 18, f64, every operation one IEEE operation in the written order:
+ *   p         (double) of the resident f32 position; T_c_w = mvo_invert_pose(T_w_c) of the observation's frame
+ *   q_r       ((R_r0 p_x + R_r1 p_y) + R_r2 p_z) + t_r;  u = (fx q_x) / q_z + cx, v likewise
+ *   e         (u - (double)uv_x, v - (double)uv_y);  e2 = e_x e_x + e_y e_y;  d = huber_delta
+ *   rho, w    e2 <= d d ? e2 : (2 d) sqrt(e2) - d d;   e2 <= d d ? 1 : d / sqrt(e2)
+ *   J         [fx / q_z, 0, -((fx q_x) / (q_z q_z)); 0, fy / q_z, -((fy q_y) / (q_z q_z))] R
+ *   H, b, chi2   the sums of w (J0c J0d + J1c J1d), w (J0c e_x + J1c e_y), rho from 0.0 in observation order
+ *   LM        lambda = 1e-3 max(H00, H11, H22); a trial solves (H + lambda I) d = -b by 3 x 3 Cholesky, p' = p + d, accepted
+ *             if every observation has q_z > 0 at p' and chi2' < chi2: the state moves, lambda *= 0.1, and the loop ends when
+ *             chi2 - chi2' <= rel_tolerance chi2; otherwise lambda *= 10; at most max_trials trials in all
+ * Observations of point i are rows obs_start[i] .. obs_start[i + 1] - 1 of obs_frame / obs_uv (the convention of
+ * mvo_map_refresh); n = mvo_map_size.  info[i] = (status, accepted steps, trials); status 0: refined, the resident position
+ * becomes (float)p; 1: fewer than min_observations observations; 2: at the start some observation sees the point at depth
+ * !(q_z > 0); 3: no trial accepted (or lambda not positive and finite at the start).  Only status 0 writes the resident
+ * position; every other status leaves its bytes untouched and reports them in pos_out.  chi2[i] = (before, after), both 0 for
+ * status 1 and 2; obs_outlier[k] = e2 > d d at the final p, 0 for status 1 and 2.
+ * MVO_ERR_INVALID: a null map, a null pointer with a positive count, obs_start[0] != 0, obs_start[n] != n_obs, a decreasing
+ * obs_start, an obs_frame outside [0, n_frames), a singular or non-finite pose, fx or fy 0 or intrinsics not finite, a non-finite
+ * obs_uv, params out of range.  MVO_ERR_CAPACITY: a point with more than 64 observations, n_frames > 64.  In every error case
+ * nothing is written.  An empty map succeeds without a launch. */
+typedef struct {
+    int32_t max_trials;       /* 1..64, default 20 */
+    int32_t min_observations; /* 2..64, default 2 */
+    double huber_delta;       /* > 0, finite; default sqrt(5.991) (ORB-SLAM, monocular) */
+    double rel_tolerance;     /* >= 0, finite; default 1e-6 */
+} mvo_map_refine_params;      /* NULL = defaults */
+/* ORB-SLAM's per-point structure-only refinement in place of vo.cpp:528-576's single two-view triangulation, the points-free
+ * half that config.yaml:123 (is_ba_fix_map_points) leaves out of the bundle adjustment.  One launch (k_map_refine); pos_out
+ * receives the resident positions after the call. */
+int mvo_map_refine_positions(mvo_ctx* ctx, mvo_map* map, const double* T_w_c /* n_frames x 16 */, int n_frames, double fx, double fy,
+                             double cx, double cy, const int32_t* obs_frame /* n_obs */, const float* obs_uv /* n_obs x 2 */,
+                             const int32_t* obs_start /* n + 1, n = mvo_map_size */, int n_obs,
+                             const mvo_map_refine_params* params, float* pos_out /* n x 3 */, double* chi2 /* n x 2 */,
+                             int32_t* info /* n x 3 */, uint8_t* obs_outlier /* n_obs, may be NULL */);
 /* ---- keyframe insertion: epipolar inlier filter, triangulation, culling ---- */
 /* geometry::helperTriangulatePoints (src/geometry/motion_estimation.cpp:214-247, called at
  * vo_addFrame.cpp:114-116): pixel2CamNormPlane on the matched pixels of the previous / current keyframe

@@ -72,6 +72,11 @@ class UndistortParams(C.Structure):
                 ("coeffs", C.c_double * 8), ("n_coeffs", C.c_int32)]
 
 
+class MapRefineParams(C.Structure):
+    """mvo_map_refine_params (include/mvo_hip.h)."""
+    _fields_ = [("max_trials", C.c_int32), ("min_observations", C.c_int32), ("huber_delta", C.c_double), ("rel_tolerance", C.c_double)]
+
+
 class InitPoses(C.Structure):
     """mvo_init_poses (include/mvo_hip.h)."""
     _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
@@ -483,6 +488,38 @@ class Context:
         self._chk(self.lib.mvo_map_refresh(self.h, m, _p(obs_desc), _p(obs_cam), _p(obs_start), len(obs_desc), _p(choice), _p(desc),
                                            _p(norm)))
         return choice, desc, norm
+
+    def map_refine_positions(self, m, T_w_c, K, obs_frame, obs_uv, obs_start, max_trials=None, min_observations=None,
+                             huber_delta=None, rel_tolerance=None):
+        """mvo_map_refine_positions: every map point's position re-estimated from all its observations with the poses fixed
+        (Huber-weighted Levenberg-Marquardt per point, in HBM) -> (pos n x 3 f32, the resident positions after the call; chi2
+        n x 2 f64: before, after; info n x 3 int32: status, accepted steps, trials; outlier n_obs uint8).  Status 0: refined,
+        1: too few observations, 2: behind a camera at the start, 3: no trial accepted.  T_w_c: n_frames x 4 x 4; observations
+        of point i: rows obs_start[i] .. obs_start[i + 1] - 1 of obs_frame (index into T_w_c) and obs_uv (pixels).  The keyword
+        arguments default to the library's (20, 2, sqrt(5.991), 1e-6)."""
+        if not hasattr(self.lib, "mvo_map_refine_positions"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_map_refine_positions")
+        T = np.ascontiguousarray(T_w_c, np.float64).reshape(-1, 16)
+        obs_frame = np.ascontiguousarray(obs_frame, np.int32).reshape(-1)
+        obs_uv = np.ascontiguousarray(obs_uv, np.float32).reshape(-1, 2)
+        obs_start = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+        if len(obs_frame) != len(obs_uv):
+            raise ValueError("one frame index per observed pixel")
+        n = self._map_size(m)
+        if len(obs_start) != n + 1:
+            raise ValueError("obs_start needs one entry per map point and one more")
+        params = None
+        if not (max_trials is None and min_observations is None and huber_delta is None and rel_tolerance is None):
+            params = MapRefineParams(20 if max_trials is None else int(max_trials), 2 if min_observations is None else int(min_observations),
+                                     float(np.sqrt(np.float64(5.991))) if huber_delta is None else float(huber_delta),
+                                     1e-6 if rel_tolerance is None else float(rel_tolerance))
+            params = C.byref(params)
+        pos, chi2, info = np.zeros((n, 3), np.float32), np.zeros((n, 2), np.float64), np.zeros((n, 3), np.int32)
+        outlier = np.zeros(len(obs_uv), np.uint8)
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        self._chk(self.lib.mvo_map_refine_positions(self.h, m, _p(T), len(T), *k, _p(obs_frame), _p(obs_uv), _p(obs_start), len(obs_uv),
+                                                    params, _p(pos), _p(chi2), _p(info), _p(outlier)))
+        return pos, chi2, info, outlier
 
     def map_debug_get(self, m):
         """mvo_debug_get_map: the resident arrays -> (pos n x 3 f32, desc n x 32)."""

@@ -314,6 +314,17 @@ struct mvo_refresh_state {  // owned by map_refresh_host.cpp, released through m
     DevBuf<uint8_t> d_in;  // one upload per call: the camera centres, the descriptors, the n + 1 starts
 };
 
+// map point positions refined from all their observations (map_refine_kernels.hip / map_refine_host.cpp)
+#define MF_MAX_FRAMES 64  // poses per call: 12 doubles each in LDS
+struct MapRefineArgs {
+    double fx, fy, cx, cy;
+    double delta, rel_tol;  // huber_delta, rel_tolerance
+    int32_t max_trials, min_obs, n_frames;
+};
+struct mvo_refine_state {  // owned by map_refine_host.cpp, released through mvo_ctx::refine_release
+    DevBuf<uint8_t> d_in;  // one upload per call: the inverted poses, the pixels, the frame indices, the n + 1 starts
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -401,6 +412,9 @@ struct mvo_ctx {
     // --- map points refreshed from their observations: allocated by the first mvo_map_refresh, released like the undistortion
     mvo_refresh_state* refresh = nullptr;
     void (*refresh_release)(mvo_ctx*) = nullptr;
+    // --- map point positions refined from their observations: allocated by the first mvo_map_refine_positions, released likewise
+    mvo_refine_state* refine = nullptr;
+    void (*refine_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -518,6 +532,10 @@ int dist_launch_ic_angle(mvo_ctx* ctx, const signed char* d_disc, int disc_n, co
 // map_refresh_kernels.hip
 int map_refresh_launch(mvo_ctx* ctx, const float* d_pos, uint8_t* d_desc, int n, const uint8_t* d_obs_desc, const double* d_obs_cam,
                        const int32_t* d_obs_start, int32_t* out_choice, uint8_t* out_desc, double* out_norm);
+// map_refine_kernels.hip
+int map_refine_launch(mvo_ctx* ctx, float* d_pos, int n, const MapRefineArgs& a, const double* d_Tcw, const float* d_uv,
+                      const int32_t* d_frame, const int32_t* d_obs_start, float* out_pos, double* out_chi2, int32_t* out_info,
+                      uint8_t* out_outlier);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -54,6 +54,16 @@
 // MPOS, in the order of MIDS: ROBS = the n + 1 observation starts (int32), RDSC / RCAM = the observations' descriptors (n_obs x
 // 32) and camera centres (n_obs x 3 f64), RPOS = the positions as resident (n x 3 f32), RCHO = the chosen observation per point
 // (int32, -1: none), RNRM = the normals (n x 3 f64); and MORD of such a frame stays what its own tracking step saw.
+// Optional key `map_point_refine_positions` (0 / 1, default 0): 1 makes every keyframe insertion while tracking refine, after the
+// culling and before the refresh above, the position of every map point from all its observations in the last 20 frames with the
+// poses fixed (my_slam/vo/map_refine.h; a Huber-weighted Levenberg-Marquardt per point); the reference sets
+// a position once from two views (vo.cpp:528-576) and its bundle adjustment keeps the points fixed (config.yaml:123).  Optional
+// keys `map_point_refine_max_trials` (default 20), `map_point_refine_huber_delta` (default sqrt(5.991)).  With the key on, a
+// keyframe's part of the frame log carries ten more records after MPOS, in the order of the map the call read: FSET = fx, fy,
+// cx, cy, max_trials, min_observations, huber_delta, rel_tolerance (f64), FTWC = the poses of the window (n_frames x 16 f64),
+// FOBS = the n + 1 observation starts (int32), FFRM / FPIX = the observations' frame indices (int32) and pixels (n_obs x 2 f32),
+// FBEF / FAFT = the positions before and after (n x 3 f32), FCHI = chi2 before and after (n x 2 f64), FINF = status, accepted
+// steps, trials (n x 3 int32), FOUT = the outlier flags (n_obs); and MORD of such a frame stays what its own tracking step saw.
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -84,6 +94,8 @@
 #pragma weak mvo_map_match_features_projection
 // ... or without the map-point refresh (`map_point_refresh`): likewise
 #pragma weak mvo_map_refresh
+// ... or without the position refinement (`map_point_refine_positions`): likewise
+#pragma weak mvo_map_refine_positions
 // ... or without the cell-wise detector (`orb_distribute_keypoints`): likewise
 #pragma weak mvo_orb_distribute_configure
 #pragma weak mvo_calc_keypoints_distributed
@@ -137,6 +149,7 @@ struct FrameLog {
         vector<int> order;
         for (const vo::MapPoint::Ptr& p : dev_map.order()) order.push_back(p->id_);
         if (fr->refreshed_) order = fr->refresh_order_before_;  // `map_point_refresh: 1`: the refresh has re-read the map since
+        if (fr->positions_refined_) order = fr->refine_order_before_;  // `map_point_refine_positions: 1`: likewise, and it came first
         vec("MORD", order);  // iteration order of Map::map_points_ when the frame looked at the map
         if (!fr->projection_pred_T_.empty()) {  // `tracking_match_by_projection: 1`: what the matcher saw
             vec("PRVP", fr->projection_prev_T_);
@@ -165,6 +178,23 @@ struct FrameLog {
         }
         triangulated(fr);
         mapAfter(map);
+        if (fr->positions_refined_) {  // `map_point_refine_positions: 1`: what the call saw and gave
+            vec("FSET", fr->refine_setup_);
+            vec("FTWC", fr->refine_T_w_c_);
+            vec("FOBS", fr->refine_obs_start_);
+            vec("FFRM", fr->refine_obs_frame_);
+            vec("FPIX", fr->refine_obs_uv_);
+            vec("FBEF", fr->refine_pos_before_);
+            vec("FAFT", fr->refine_pos_after_);
+            vec("FCHI", fr->refine_chi2_);
+            vec("FINF", fr->refine_info_);
+            vec("FOUT", fr->refine_outlier_);
+            int n_refined = 0, n_flagged = 0;
+            for (size_t i = 0; i < fr->refine_info_.size(); i += 3) n_refined += fr->refine_info_[i] == 0 ? 1 : 0;
+            for (unsigned char c : fr->refine_outlier_) n_flagged += c ? 1 : 0;
+            printf("frame %d: %d of %d map point positions refined from %d observations (%d flagged as outliers)\n", fr->id_, n_refined,
+                   (int)fr->refine_info_.size() / 3, fr->refine_obs_start_.back(), n_flagged);  // (with or without a log file)
+        }
         if (fr->refreshed_) {  // `map_point_refresh: 1`: what the refresh saw and gave
             vec("ROBS", fr->refresh_obs_start_);
             vec("RDSC", fr->refresh_obs_desc_);
@@ -298,6 +328,11 @@ int main(int argc, char** argv) {
         if (vo::mapPointRefresh()) {
             if (!mvo_map_refresh) throw std::runtime_error("map_point_refresh: this libmvo_hip.so has no mvo_map_refresh");
             printf("map points take descriptor and normal from their observations at every keyframe\n");
+        }
+        if (vo::mapPointRefinePositions()) {
+            if (!mvo_map_refine_positions)
+                throw std::runtime_error("map_point_refine_positions: this libmvo_hip.so has no mvo_map_refine_positions");
+            printf("map point positions are refined from all their observations at every keyframe\n");
         }
         if (geometry::orbDistributeKeypoints()) {
             if (!mvo_orb_distribute_configure || !mvo_calc_keypoints_distributed)

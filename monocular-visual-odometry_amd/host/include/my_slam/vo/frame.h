@@ -68,6 +68,24 @@ public:
     vector<int> refresh_choice_;
     vector<double> refresh_norm_;
     bool refreshed_ = false;
+    // (not in the reference) `map_point_refine_positions: 1`, on the keyframe after whose insertion the map point positions
+    // were refined (my_slam/vo/map_refine.h): the ids of MapOnDevice::order() as the frame's own tracking step saw it, then
+    // what the call saw and gave, in the order of the map it read: the intrinsics and parameters (fx, fy, cx, cy, max_trials,
+    // min_observations, huber_delta, rel_tolerance), the poses of frames_buff_ (n_frames x 16), the observation starts
+    // (n + 1), frame indices and pixels (n_obs, n_obs x 2), the positions before and after (n x 3 each), chi2 (n x 2), info
+    // (n x 3), the outlier flags (n_obs); empty otherwise
+    vector<int> refine_order_before_;
+    vector<double> refine_setup_;
+    vector<double> refine_T_w_c_;
+    vector<int> refine_obs_start_;
+    vector<int> refine_obs_frame_;
+    vector<float> refine_obs_uv_;
+    vector<float> refine_pos_before_;
+    vector<float> refine_pos_after_;
+    vector<double> refine_chi2_;
+    vector<int> refine_info_;
+    vector<unsigned char> refine_outlier_;
+    bool positions_refined_ = false;
     // (not in the reference) `orb_distribute_keypoints: 1`: per pyramid level, the candidates of calcKeyPoints and the key
     // points it kept (before calcDescriptors drops those near the image border); empty otherwise
     vector<int> distribute_candidates_per_level_;
@@ -98,6 +116,17 @@ public:
         refresh_pos_.clear();
         refresh_choice_.clear();
         refresh_norm_.clear();
+        refine_order_before_.clear();  // (logged by now; positions_refined_ stays)
+        refine_setup_.clear();
+        refine_T_w_c_.clear();
+        refine_obs_start_.clear();
+        refine_obs_frame_.clear();
+        refine_obs_uv_.clear();
+        refine_pos_before_.clear();
+        refine_pos_after_.clear();
+        refine_chi2_.clear();
+        refine_info_.clear();
+        refine_outlier_.clear();
     }
     void calcKeyPoints() {
         if (geometry::orbDistributeKeypoints())  // the ORB-SLAM way (my_slam/geometry/orb_distribute.h)

@@ -32,6 +32,9 @@ struct MapObservations {  // the three input arrays of mvo_map_refresh
     vector<int> obs_start;           // n + 1
     vector<unsigned char> obs_desc;  // n_obs x 32
     vector<double> obs_cam;          // n_obs x 3
+    // the same observations as mvo_map_refine_positions takes them (my_slam/vo/map_refine.h)
+    vector<int> obs_frame;  // n_obs: position of the frame in frames_buff
+    vector<float> obs_uv;   // n_obs x 2: keypoints_[k].pt
 };
 
 inline MapObservations collectObservations(const std::deque<Frame::Ptr>& frames_buff, const vector<MapPoint::Ptr>& order) {
@@ -63,6 +66,10 @@ inline MapObservations collectObservations(const std::deque<Frame::Ptr>& frames_
             const unsigned char* d = fr->descriptors_.ptr<unsigned char>(v[k].kpt);
             o.obs_desc.insert(o.obs_desc.end(), d, d + 32);
             for (int r = 0; r < 3; ++r) o.obs_cam.push_back(fr->T_w_c_.at<double>(r, 3));
+            o.obs_frame.push_back(v[k].frame);
+            const bool has_kpt = v[k].kpt < (int)fr->keypoints_.size();  // (a hand-built frame may carry descriptors only)
+            o.obs_uv.push_back(has_kpt ? fr->keypoints_[v[k].kpt].pt.x : 0.f);
+            o.obs_uv.push_back(has_kpt ? fr->keypoints_[v[k].kpt].pt.y : 0.f);
         }
         o.obs_start.push_back((int)(o.obs_desc.size() / 32));
     }
@@ -109,4 +116,6 @@ inline void refreshMapPoints(TrackingState& st, const Frame::Ptr& curr) {
 
 }  // namespace vo
 }  // namespace my_slam
+
+#include "my_slam/vo/map_refine.h"  // (shares collectObservations; declared in tracking_loop.h)
 #endif

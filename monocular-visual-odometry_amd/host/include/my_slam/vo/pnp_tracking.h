@@ -118,6 +118,8 @@ public:
     const vector<unsigned char>& descriptors() const { return desc_; }  // n x 32
     // the map-point refresh (my_slam/vo/map_refresh.h) has rewritten row i in HBM: the host copy follows
     void setDescriptor(int i, const unsigned char* d) { std::memcpy(&desc_[32 * (size_t)i], d, 32); }
+    // the position refinement (my_slam/vo/map_refine.h) has rewritten row i in HBM: the host copy follows
+    void setPosition(int i, const float* p) { std::memcpy(&pos_[3 * (size_t)i], p, 12); }
 
 private:
     mvo_map* map_ = nullptr;

@@ -36,6 +36,14 @@ inline bool mapPointRefresh() {  // the optional key, latched on first use
     return on;
 }
 
+// my_slam/vo/map_refine.h (included at the end of map_refresh.h, whose traversal it shares): the position refinement of `map_point_refine_positions: 1`
+inline void refineMapPointPositions(TrackingState& st, const cv::Mat& K, const Frame::Ptr& curr = nullptr);
+inline bool mapPointRefinePositions() {  // the optional key, latched on first use
+    static const bool on =
+        basics::Config::has("map_point_refine_positions") && basics::Config::get<int>("map_point_refine_positions") != 0;
+    return on;
+}
+
 inline cv::Point3f preTranslatePoint3f(const cv::Point3f& p, const cv::Mat& T) {  // opencv_funcs.cpp:67-78
     const double q[4] = {p.x, p.y, p.z, 1};
     double res[3] = {0, 0, 0};
@@ -149,6 +157,7 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
             triangulateWithReferenceKeyframe(curr, st.ref_, K);
             pushCurrPointsToMap(st, curr);
             optimizeMap(st, curr, K);
+            if (mapPointRefinePositions()) refineMapPointPositions(st, K, curr);  // positions from all observations, poses fixed
             if (mapPointRefresh()) refreshMapPoints(st, curr);  // descriptor and normal from all observations in the window
             st.map_->insertKeyFrame(curr);  // addKeyFrame_
             st.ref_ = curr;
