@@ -487,6 +487,56 @@ int mvo_map_refine_positions(mvo_ctx* ctx, mvo_map* map, const double* T_w_c /* 
                              const int32_t* obs_start /* n + 1, n = mvo_map_size */, int n_obs,
                              const mvo_map_refine_params* params, float* pos_out /* n x 3 */, double* chi2 /* n x 2 */,
                              int32_t* info /* n x 3 */, uint8_t* obs_outlier /* n_obs, may be NULL */);
+/* ---- duplicate map points fused over the buffered frames ---------------------------------------- */
+/* The reference creates a map point whenever the matched keypoint of the previous keyframe is not one already
+ * (pushCurrPointsToMap_, vo.cpp:528-576), even when the current keypoint is connected to a map point through the PnP inliers:
+ * one physical point enters the map under several ids, each with part of the observations, and a buffered frame that sees a
+ * point without having matched it contributes nothing.  ORB-SLAM's local mapping answers both with SearchInNeighbors:
+ * ORBmatcher::Fuse projects every map point into every neighbouring keyframe, and MapPoint::Replace merges two points that
+ * claim one keypoint.  Declared operation by operation in DESIGN.md section 19:
+ *   seen[i]     64-bit mask, bit f set when some conn[f][j] == i
+ *   search      per (frame f, map point i): the projection, in_view and the gate of mvo_map_match_knn2_projection with
+ *               T_c_w[f] = mvo_invert_pose(T_w_c[f]); active = in_view && !(seen[i] >> f & 1); r2[j] = (max_px scale[j])^2, and
+ *               -1.0 for a keypoint with conn == -2, which never passes; the two nearest gated keypoints, equal distances keep
+ *               the lower keypoint; a pair that is not active writes the "not in view" row
+ *   candidate   (d, f, i, j) with j = idx0 >= 0 and d = dist0 <= max_hamming; no ratio test
+ *   claimant    per (f, j) the candidate with the smallest d, then the lower i, wins
+ *   merges      the winners with conn[f][j] = i2 >= 0 in ascending (d, f, i), union-find over the map rows, a component's mask the
+ *               OR of its members' seen: same component -> nothing; masks intersect -> refused (two points observed in one frame
+ *               are two points); else united
+ *   additions   after all merges the winners with conn[f][j] == -1 in the same order: bit f of the component's mask set ->
+ *               refused; else the bit is set and (f, j, survivor) appended to `added`
+ *   survivor    of a component: the member with the largest popcount of its own seen, the lower row on a tie;
+ *               replaced_by[i] = the survivor's row (i itself for a point no merge touched)
+ * MVO_ERR_INVALID: a null map, a null pointer with a positive count, a conn outside [-2, n_map), a singular or non-finite pose,
+ * fx or fy 0, cols or rows <= 0, max_px negative or NaN, a scale entry negative or not finite, max_hamming outside 0..256.
+ * MVO_ERR_CAPACITY: n_frames > 64, a frame with more than 65535 keypoints, cap_added too small (*n_added is set).  Every other
+ * check precedes the upload, and on error nothing else is written.  An empty map or n_frames == 0 succeeds without a launch; a
+ * frame with n == 0 succeeds.  Neither call changes the resident arrays: the caller removes the replaced rows. */
+typedef struct {
+    const uint8_t* desc;   /* n x 32 */
+    const float* xy;       /* n x 2 */
+    const float* scale;    /* n or NULL: the t_scale of mvo_map_match_knn2_projection */
+    const int32_t* conn;   /* n: >= 0 the map row this keypoint is connected to, -1 free, -2 connected to a point that left
+                              the map */
+    int32_t n;             /* 0..65535 */
+    double T_w_c[16];
+} mvo_fuse_frame;
+typedef struct { int32_t frame, keypoint, point; } mvo_fuse_observation;
+typedef struct { double max_px; int32_t max_hamming; } mvo_map_fuse_params; /* NULL = defaults: 3.0, 50 */
+/* ORB-SLAM ORBmatcher::Fuse (the projection search of every map point in every neighbouring keyframe) where vo.cpp:528-576 only
+ * ever creates points.  Raw: n_frames blocks of one row per map point, each row by the conventions of
+ * mvo_map_match_knn2_projection (not active: px (0, 0), idx (-1, -1), dist (INT32_MAX, INT32_MAX), n_candidates -1).  One upload,
+ * one launch (k_map_fuse_search), one wait.  idx / dist: n_frames x n_map x 2 int32; n_candidates (n_frames x n_map) and px
+ * (n_frames x n_map x 2 f32) are optional. */
+int mvo_map_fuse_search(mvo_ctx* ctx, mvo_map* map, const mvo_fuse_frame* frames, int n_frames, double fx, double fy, double cx,
+                        double cy, int cols, int rows, double max_px, int32_t* idx, int32_t* dist, int32_t* n_candidates, float* px);
+/* ORB-SLAM ORBmatcher::Fuse + MapPoint::Replace in place of vo.cpp:528-576's unconditional new point: the search above, then the
+ * rule on the host.  replaced_by: n_map rows; added: up to cap_added observations, *n_added of them written; counts[6] =
+ * candidates, merges accepted, merges refused, observations added, observations refused, points replaced. */
+int mvo_map_fuse(mvo_ctx* ctx, mvo_map* map, const mvo_fuse_frame* frames, int n_frames, double fx, double fy, double cx, double cy,
+                 int cols, int rows, const mvo_map_fuse_params* params, int32_t* replaced_by /* n_map */,
+                 mvo_fuse_observation* added, int cap_added, int* n_added, int32_t* counts /* 6 */);
 /* ---- keyframe insertion: epipolar inlier filter, triangulation, culling ---- */
 /* geometry::helperTriangulatePoints (src/geometry/motion_estimation.cpp:214-247, called at
  * vo_addFrame.cpp:114-116): pixel2CamNormPlane on the matched pixels of the previous / current keyframe

@@ -77,6 +77,20 @@ class MapRefineParams(C.Structure):
     _fields_ = [("max_trials", C.c_int32), ("min_observations", C.c_int32), ("huber_delta", C.c_double), ("rel_tolerance", C.c_double)]
 
 
+class FuseFrame(C.Structure):
+    """mvo_fuse_frame (include/mvo_hip.h)."""
+    _fields_ = [("desc", C.c_void_p), ("xy", C.c_void_p), ("scale", C.c_void_p), ("conn", C.c_void_p), ("n", C.c_int32),
+                ("T_w_c", C.c_double * 16)]
+
+
+class MapFuseParams(C.Structure):
+    """mvo_map_fuse_params (include/mvo_hip.h)."""
+    _fields_ = [("max_px", C.c_double), ("max_hamming", C.c_int32)]
+
+
+FUSE_OBSERVATION_DTYPE = np.dtype([("frame", np.int32), ("keypoint", np.int32), ("point", np.int32)])
+
+
 class InitPoses(C.Structure):
     """mvo_init_poses (include/mvo_hip.h)."""
     _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
@@ -520,6 +534,66 @@ class Context:
         self._chk(self.lib.mvo_map_refine_positions(self.h, m, _p(T), len(T), *k, _p(obs_frame), _p(obs_uv), _p(obs_start), len(obs_uv),
                                                     params, _p(pos), _p(chi2), _p(info), _p(outlier)))
         return pos, chi2, info, outlier
+
+    # ---- duplicate map points fused over the buffered frames (ORB-SLAM's ORBmatcher::Fuse / MapPoint::Replace)
+    @staticmethod
+    def _fuse_frames(frames):
+        """frames: a sequence of dicts with desc (n x 32), xy (n x 2), conn (n), T (4 x 4, camera to world) and optionally
+        scale (n) -> (the mvo_fuse_frame array, the keypoint counts, the arrays it points into)."""
+        arr, counts, keep = (FuseFrame * max(len(frames), 1))(), [], []
+        for f, fr in enumerate(frames):
+            desc = np.ascontiguousarray(fr["desc"], np.uint8).reshape(-1, 32)
+            xy = np.ascontiguousarray(fr["xy"], np.float32).reshape(-1, 2)
+            conn = np.ascontiguousarray(fr["conn"], np.int32).reshape(-1)
+            scale = fr.get("scale")
+            if scale is not None:
+                scale = np.ascontiguousarray(scale, np.float32).reshape(-1)
+            if len(xy) != len(desc) or len(conn) != len(desc) or (scale is not None and len(scale) != len(desc)):
+                raise ValueError("frame %d: one position, one connection (and one scale) per descriptor" % f)
+            keep.append((desc, xy, conn, scale))
+            arr[f].desc, arr[f].xy, arr[f].conn = desc.ctypes.data, xy.ctypes.data, conn.ctypes.data
+            arr[f].scale = None if scale is None else scale.ctypes.data
+            arr[f].n = len(desc)
+            arr[f].T_w_c[:] = [float(x) for x in np.asarray(fr["T"], np.float64).reshape(16)]
+            counts.append(len(desc))
+        return arr, counts, keep
+
+    def map_fuse_search(self, m, frames, K, cols, rows, max_px):
+        """mvo_map_fuse_search: every map point against every keypoint of every frame in one launch -> (idx F x n_map x 2,
+        dist F x n_map x 2, n_candidates F x n_map, px F x n_map x 2 f32), per frame the rows of map_match_knn2_projection; a
+        point not in view of the frame or already connected in it: idx -1, dist INT32_MAX, n_candidates -1, px (0, 0)."""
+        if not hasattr(self.lib, "mvo_map_fuse_search"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_map_fuse_search")
+        arr, _, keep = self._fuse_frames(frames)
+        n, F = self._map_size(m), len(frames)
+        idx, dist = np.zeros((F, n, 2), np.int32), np.zeros((F, n, 2), np.int32)
+        cnt, px = np.zeros((F, n), np.int32), np.zeros((F, n, 2), np.float32)
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        self._chk(self.lib.mvo_map_fuse_search(self.h, m, arr, F, *k, int(cols), int(rows), C.c_double(max_px), _p(idx), _p(dist),
+                                               _p(cnt), _p(px)))
+        del keep
+        return idx, dist, cnt, px
+
+    def map_fuse(self, m, frames, K, cols, rows, max_px=None, max_hamming=None, cap_added=None):
+        """mvo_map_fuse: the search, then one claimant per keypoint, the merges and the additions -> (replaced_by n_map int32:
+        the row that stands for each point from now on; added, FUSE_OBSERVATION_DTYPE: the observations gained, `point` a
+        surviving row; counts 6 int32: candidates, merges accepted, merges refused, observations added, observations refused,
+        points replaced).  The resident map is not changed.  max_px / max_hamming default to the library's (3.0, 50)."""
+        if not hasattr(self.lib, "mvo_map_fuse"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_map_fuse")
+        arr, counts_kp, keep = self._fuse_frames(frames)
+        n, F = self._map_size(m), len(frames)
+        params = None
+        if not (max_px is None and max_hamming is None):
+            params = C.byref(MapFuseParams(3.0 if max_px is None else float(max_px), 50 if max_hamming is None else int(max_hamming)))
+        cap = sum(counts_kp) if cap_added is None else int(cap_added)
+        replaced_by, added = np.zeros(n, np.int32), np.zeros(max(cap, 1), FUSE_OBSERVATION_DTYPE)
+        n_added, counts = C.c_int(), np.zeros(6, np.int32)
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        self._chk(self.lib.mvo_map_fuse(self.h, m, arr, F, *k, int(cols), int(rows), params, _p(replaced_by), _p(added), cap,
+                                        C.byref(n_added), _p(counts)))
+        del keep
+        return replaced_by, added[:n_added.value].copy(), counts
 
     def map_debug_get(self, m):
         """mvo_debug_get_map: the resident arrays -> (pos n x 3 f32, desc n x 32)."""

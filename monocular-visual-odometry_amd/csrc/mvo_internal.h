@@ -325,6 +325,24 @@ struct mvo_refine_state {  // owned by map_refine_host.cpp, released through mvo
     DevBuf<uint8_t> d_in;  // one upload per call: the inverted poses, the pixels, the frame indices, the n + 1 starts
 };
 
+// duplicate map points fused over the buffered frames (map_fuse_kernels.hip / map_fuse_host.cpp)
+struct MapFuseArgs {
+    double fx, fy, cx, cy;
+    int cols, rows;
+};
+struct MapFuseFrame {  // one row of k_map_fuse_search's per-frame table, read from HBM (128 bytes)
+    double T[12];      // rows 0..2 of T_c_w = inv(T_w_c)
+    const uint4* t;    // nt x 32 descriptor bytes
+    const double* tg;  // nt x ((double)x, (double)y, r2), r2 = -1.0 for a keypoint that never passes
+    int32_t nt, slice; // slice = guided_slice(nt, the launch's train groups)
+    int32_t pad[2];
+};
+struct mvo_fuse_state {  // owned by map_fuse_host.cpp, released through mvo_ctx::fuse_release
+    DevBuf<uint8_t> d_in;      // one upload per call: the frame table, the seen masks, the parked keypoints, the descriptors
+    DevBuf<uint8_t> d_part;    // partial key pairs and counts of guided_knn2(), one block per frame
+    DevBuf<int32_t> d_arrive;  // arrival counters, one per (frame, group of 64 map points): self re-arming, zeroed when allocated
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -415,6 +433,9 @@ struct mvo_ctx {
     // --- map point positions refined from their observations: allocated by the first mvo_map_refine_positions, released likewise
     mvo_refine_state* refine = nullptr;
     void (*refine_release)(mvo_ctx*) = nullptr;
+    // --- duplicate map points fused over the buffered frames: allocated by the first mvo_map_fuse*, released likewise
+    mvo_fuse_state* fuse = nullptr;
+    void (*fuse_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -536,6 +557,9 @@ int map_refresh_launch(mvo_ctx* ctx, const float* d_pos, uint8_t* d_desc, int n,
 int map_refine_launch(mvo_ctx* ctx, float* d_pos, int n, const MapRefineArgs& a, const double* d_Tcw, const float* d_uv,
                       const int32_t* d_frame, const int32_t* d_obs_start, float* out_pos, double* out_chi2, int32_t* out_info,
                       uint8_t* out_outlier);
+// map_fuse_kernels.hip
+int map_fuse_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, int n_map, const MapFuseArgs& a, const MapFuseFrame* d_frames,
+                    int n_frames, int ngroups, const unsigned long long* d_seen, GuidedPartials part, int32_t* out);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -64,6 +64,17 @@
 // FOBS = the n + 1 observation starts (int32), FFRM / FPIX = the observations' frame indices (int32) and pixels (n_obs x 2 f32),
 // FBEF / FAFT = the positions before and after (n x 3 f32), FCHI = chi2 before and after (n x 2 f64), FINF = status, accepted
 // steps, trials (n x 3 int32), FOUT = the outlier flags (n_obs); and MORD of such a frame stays what its own tracking step saw.
+// Optional key `map_point_fuse` (0 / 1, default 0): 1 makes every keyframe insertion while tracking fuse, after the culling and
+// before the refinement and the refresh above, the map points that are one physical point, and connect every buffered frame that
+// sees a point without having matched it (my_slam/vo/map_fuse.h; ORB-SLAM's ORBmatcher::Fuse and MapPoint::Replace, DESIGN.md
+// section 19); the reference creates a new point whenever the matched keypoint of the previous keyframe is none (vo.cpp:528-576).
+// Optional keys `map_point_fuse_max_px` (default 3.0), `map_point_fuse_max_hamming` (default 50).  With the key on, a keyframe's part
+// of the frame log carries fourteen more records after MPOS: USET = fx, fy, cx, cy, cols, rows, max_px, max_hamming (f64), UMID /
+// UPOS / UMDS = the ids, positions (n x 3 f32) and descriptors (n x 32) of the map the call read, UKPN = the keypoints per
+// buffered frame (int32), UTWC = their poses (n_frames x 16 f64), UDSC / UPIX / USCL / UCON = frame after frame the descriptors,
+// pixels (f32), scales (f32) and connections (int32: map row, -1 free, -2 a point that left the map), UREP = replaced_by (n
+// int32), UADD = the added observations (frame, keypoint, point: n_added x 3 int32), UCNT = the six counts, UIDS = the ids of the
+// map after the call in its new iteration order; and MORD of such a frame stays what its own tracking step saw.
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -96,6 +107,8 @@
 #pragma weak mvo_map_refresh
 // ... or without the position refinement (`map_point_refine_positions`): likewise
 #pragma weak mvo_map_refine_positions
+// ... or without the fusion of duplicate map points (`map_point_fuse`): likewise
+#pragma weak mvo_map_fuse
 // ... or without the cell-wise detector (`orb_distribute_keypoints`): likewise
 #pragma weak mvo_orb_distribute_configure
 #pragma weak mvo_calc_keypoints_distributed
@@ -150,6 +163,7 @@ struct FrameLog {
         for (const vo::MapPoint::Ptr& p : dev_map.order()) order.push_back(p->id_);
         if (fr->refreshed_) order = fr->refresh_order_before_;  // `map_point_refresh: 1`: the refresh has re-read the map since
         if (fr->positions_refined_) order = fr->refine_order_before_;  // `map_point_refine_positions: 1`: likewise, and it came first
+        if (fr->fused_) order = fr->fuse_order_before_;  // `map_point_fuse: 1`: likewise, and it came before both
         vec("MORD", order);  // iteration order of Map::map_points_ when the frame looked at the map
         if (!fr->projection_pred_T_.empty()) {  // `tracking_match_by_projection: 1`: what the matcher saw
             vec("PRVP", fr->projection_prev_T_);
@@ -178,6 +192,25 @@ struct FrameLog {
         }
         triangulated(fr);
         mapAfter(map);
+        if (fr->fused_) {  // `map_point_fuse: 1`: what the call saw and gave
+            vec("USET", fr->fuse_setup_);
+            vec("UMID", fr->fuse_map_ids_);
+            vec("UPOS", fr->fuse_map_pos_);
+            vec("UMDS", fr->fuse_map_desc_);
+            vec("UKPN", fr->fuse_kp_count_);
+            vec("UTWC", fr->fuse_T_w_c_);
+            vec("UDSC", fr->fuse_desc_);
+            vec("UPIX", fr->fuse_xy_);
+            vec("USCL", fr->fuse_scale_);
+            vec("UCON", fr->fuse_conn_);
+            vec("UREP", fr->fuse_replaced_by_);
+            vec("UADD", fr->fuse_added_);
+            vec("UCNT", fr->fuse_counts_);
+            vec("UIDS", fr->fuse_map_ids_after_);
+            const vector<int>& c = fr->fuse_counts_;
+            printf("frame %d: %d of %d map points fused into others (%d merges refused), %d observations added (%d refused) of %d candidates\n",
+                   fr->id_, c[5], (int)fr->fuse_replaced_by_.size(), c[2], c[3], c[4], c[0]);  // (with or without a log file)
+        }
         if (fr->positions_refined_) {  // `map_point_refine_positions: 1`: what the call saw and gave
             vec("FSET", fr->refine_setup_);
             vec("FTWC", fr->refine_T_w_c_);
@@ -333,6 +366,10 @@ int main(int argc, char** argv) {
             if (!mvo_map_refine_positions)
                 throw std::runtime_error("map_point_refine_positions: this libmvo_hip.so has no mvo_map_refine_positions");
             printf("map point positions are refined from all their observations at every keyframe\n");
+        }
+        if (vo::mapPointFuse()) {
+            if (!mvo_map_fuse) throw std::runtime_error("map_point_fuse: this libmvo_hip.so has no mvo_map_fuse");
+            printf("duplicate map points are fused and missed observations added at every keyframe\n");
         }
         if (geometry::orbDistributeKeypoints()) {
             if (!mvo_orb_distribute_configure || !mvo_calc_keypoints_distributed)

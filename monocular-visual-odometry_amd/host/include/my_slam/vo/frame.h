@@ -86,6 +86,27 @@ public:
     vector<int> refine_info_;
     vector<unsigned char> refine_outlier_;
     bool positions_refined_ = false;
+    // (not in the reference) `map_point_fuse: 1`, on the keyframe after whose insertion duplicate map points were fused
+    // (my_slam/vo/map_fuse.h): the ids of MapOnDevice::order() as the frame's own tracking step saw it, then what the call saw and
+    // gave: the intrinsics, image size and parameters (fx, fy, cx, cy, cols, rows, max_px, max_hamming), the map as resident (ids,
+    // n x 3 positions, n x 32 descriptors), the frames of frames_buff_ (keypoints per frame, n_frames x 16 poses, then frame after
+    // frame the descriptors, pixels, scales and connections), replaced_by (n), added (n_added x 3), counts (6) and the ids of the
+    // map after the call; empty otherwise
+    vector<int> fuse_order_before_;
+    vector<double> fuse_setup_;
+    vector<int> fuse_map_ids_;
+    vector<float> fuse_map_pos_;
+    vector<unsigned char> fuse_map_desc_;
+    vector<int> fuse_kp_count_;
+    vector<double> fuse_T_w_c_;
+    vector<unsigned char> fuse_desc_;
+    vector<float> fuse_xy_, fuse_scale_;
+    vector<int> fuse_conn_;
+    vector<int> fuse_replaced_by_;
+    vector<int> fuse_added_;
+    vector<int> fuse_counts_;
+    vector<int> fuse_map_ids_after_;
+    bool fused_ = false;
     // (not in the reference) `orb_distribute_keypoints: 1`: per pyramid level, the candidates of calcKeyPoints and the key
     // points it kept (before calcDescriptors drops those near the image border); empty otherwise
     vector<int> distribute_candidates_per_level_;
@@ -127,6 +148,21 @@ public:
         refine_chi2_.clear();
         refine_info_.clear();
         refine_outlier_.clear();
+        fuse_order_before_.clear();  // (logged by now; fused_ stays)
+        fuse_setup_.clear();
+        fuse_map_ids_.clear();
+        fuse_map_pos_.clear();
+        fuse_map_desc_.clear();
+        fuse_kp_count_.clear();
+        fuse_T_w_c_.clear();
+        fuse_desc_.clear();
+        fuse_xy_.clear();
+        fuse_scale_.clear();
+        fuse_conn_.clear();
+        fuse_replaced_by_.clear();
+        fuse_added_.clear();
+        fuse_counts_.clear();
+        fuse_map_ids_after_.clear();
     }
     void calcKeyPoints() {
         if (geometry::orbDistributeKeypoints())  // the ORB-SLAM way (my_slam/geometry/orb_distribute.h)

@@ -85,4 +85,6 @@ inline void refineMapPointPositions(TrackingState& st, const cv::Mat& K, const F
 
 }  // namespace vo
 }  // namespace my_slam
+
+#include "my_slam/vo/map_fuse.h"  // (declared in tracking_loop.h)
 #endif

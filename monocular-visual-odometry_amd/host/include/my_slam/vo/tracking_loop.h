@@ -44,6 +44,13 @@ inline bool mapPointRefinePositions() {  // the optional key, latched on first u
     return on;
 }
 
+// my_slam/vo/map_fuse.h (included at the end of map_refine.h): the fusion of duplicate map points of `map_point_fuse: 1`
+inline void fuseMapPoints(TrackingState& st, const cv::Mat& K, const Frame::Ptr& curr = nullptr);
+inline bool mapPointFuse() {  // the optional key, latched on first use
+    static const bool on = basics::Config::has("map_point_fuse") && basics::Config::get<int>("map_point_fuse") != 0;
+    return on;
+}
+
 inline cv::Point3f preTranslatePoint3f(const cv::Point3f& p, const cv::Mat& T) {  // opencv_funcs.cpp:67-78
     const double q[4] = {p.x, p.y, p.z, 1};
     double res[3] = {0, 0, 0};
@@ -157,6 +164,7 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
             triangulateWithReferenceKeyframe(curr, st.ref_, K);
             pushCurrPointsToMap(st, curr);
             optimizeMap(st, curr, K);
+            if (mapPointFuse()) fuseMapPoints(st, K, curr);  // one point per physical point, every observation in the window
             if (mapPointRefinePositions()) refineMapPointPositions(st, K, curr);  // positions from all observations, poses fixed
             if (mapPointRefresh()) refreshMapPoints(st, curr);  // descriptor and normal from all observations in the window
             st.map_->insertKeyFrame(curr);  // addKeyFrame_
