@@ -537,6 +537,64 @@ int mvo_map_fuse_search(mvo_ctx* ctx, mvo_map* map, const mvo_fuse_frame* frames
 int mvo_map_fuse(mvo_ctx* ctx, mvo_map* map, const mvo_fuse_frame* frames, int n_frames, double fx, double fy, double cx, double cy,
                  int cols, int rows, const mvo_map_fuse_params* params, int32_t* replaced_by /* n_map */,
                  mvo_fuse_observation* added, int cap_added, int* n_added, int32_t* counts /* 6 */);
+/* ---- new map points triangulated against every buffered frame ------------------------------------ */
+/* The reference triangulates a new keyframe against its reference keyframe only (triangulateWithReferenceKeyframe,
+ * vo_addFrame.cpp:104-116; pushCurrPointsToMap_, vo.cpp:528-576): a keypoint without a partner there, or with too little
+ * parallax, gets no map point although the other buffered frames see it from wider baselines.  ORB-SLAM's local mapping has
+ * LocalMapping::CreateNewMapPoints: every keypoint without a map point is searched along its epipolar line in every
+ * neighbouring keyframe, triangulated and verified.  Declared operation by operation in DESIGN.md section 20:
+ *   frame f     M_f = mvo_invert_pose(T_w_c_curr) T_w_c_f (R_f, t_f its rows), F_f = mvo_fundamental_from_poses(curr, f);
+ *               active when b2 = (tx tx + ty ty) + tz tz satisfies b2 > 0 && b2 >= min_baseline^2
+ *   search      per (frame f, keypoint i of curr): the line and the gate of mvo_match_knn2_epipolar with F_f; active = conn_c[i]
+ *               == -1 && frame active && nrm > 0; tol2[j] = (max_line_px scale_f[j])^2, and -1.0 for a keypoint of f with
+ *               conn != -1, which never passes; the two nearest gated keypoints, equal distances keep the lower keypoint; a pair
+ *               that is not active writes idx (-1, -1), dist (INT32_MAX, INT32_MAX), n_candidates -1
+ *   pairs       per frame the filter of mvo_match_features_epipolar (ceiling, ratio, one query per train); ordered by (f, j)
+ *   verify      per pair pw::triangulate_match(xy_f[j], xy_c[i], R_f, t_f) = the arithmetic of mvo_triangulate_points, then
+ *               status = 1 (a float not finite) | 2 (a depth not positive) | 4 (parallax: dot <= 0 or cos2 >= max_cos_parallax^2)
+ *               | 8, 16 (reprojection in f, in curr: e2 > max_reproj_chi2 scale^2) | 32 (scale consistency against ratio_factor)
+ *   choice      per keypoint of curr the pair with status 0 and the smallest cos2, then the lower frame; sorted by keypoint
+ * MVO_ERR_INVALID: a null pointer with a positive count, a singular or non-finite pose, fx or fy 0 or non-finite intrinsics, a
+ * negative or NaN max_line_px, min_baseline, max_reproj_chi2 or ratio_factor, lowe_ratio NaN, max_cos_parallax outside [0, 1],
+ * max_hamming outside 0..256, a scale entry negative or not finite.  MVO_ERR_CAPACITY: n_frames > 64, more than 65535 keypoints
+ * in a frame or in curr, cap_points or cap_pairs too small (*n_points, *n_pairs are set, nothing else is written).  Every check
+ * precedes the upload, and on error nothing else is written.  n_frames == 0, no free keypoint and no pair succeed without the
+ * launch they would feed.  No resident map is read or changed.  Only conn == -1 ("free") matters in a frame and in curr. */
+typedef struct {
+    double max_line_px;       /* 2.0 */
+    double lowe_ratio;        /* 0.8 */
+    int32_t max_hamming;      /* 64 */
+    double max_cos_parallax;  /* 0.9998 */
+    double max_reproj_chi2;   /* 5.991 */
+    double ratio_factor;      /* 1.8 */
+    double min_baseline;      /* 0.0 */
+} mvo_window_triangulate_params; /* NULL = the defaults beside the fields */
+typedef struct {
+    int32_t frame, keypoint, train, hamming, status;
+    float p_curr[3], p_frame[3]; /* the point in the camera of curr, in the camera of the frame */
+    double cos2;
+} mvo_window_pair;
+typedef struct {
+    int32_t keypoint, frame, train, hamming;
+    float p_curr[3];
+    double cos2;
+} mvo_window_point;
+/* ORB-SLAM ORBmatcher::SearchForTriangulation against every neighbouring keyframe where vo_addFrame.cpp:104-116 has one pair of
+ * views.  Raw: n_frames blocks of one row per keypoint of curr, each row by the conventions of mvo_match_knn2_epipolar.  One
+ * upload, one launch (k_window_epipolar_search), one wait.  idx / dist: n_frames x curr->n x 2 int32; n_candidates (n_frames x
+ * curr->n) is optional. */
+int mvo_window_triangulate_search(mvo_ctx* ctx, const mvo_fuse_frame* curr, const mvo_fuse_frame* frames, int n_frames, double fx,
+                                  double fy, double cx, double cy, double max_line_px, double min_baseline, int32_t* idx,
+                                  int32_t* dist, int32_t* n_candidates);
+/* ORB-SLAM LocalMapping::CreateNewMapPoints in place of vo_addFrame.cpp:104-116's single pair of views: one upload, the search
+ * launch, one wait, the filter, one small upload, the verification launch (k_window_verify), one wait, the choice.  points: up
+ * to cap_points, *n_points of them written; pairs (may be NULL, then cap_pairs and n_pairs are not looked at): every pair after
+ * the filter with its status; counts[12] = free keypoints of curr, active frames, rows with idx0 >= 0, pairs after the filter,
+ * pairs failing bit 1, 2, 4, 8, 16, 32, accepted pairs, new points. */
+int mvo_window_triangulate(mvo_ctx* ctx, const mvo_fuse_frame* curr, const mvo_fuse_frame* frames, int n_frames, double fx, double fy,
+                           double cx, double cy, const mvo_window_triangulate_params* params, mvo_window_point* points,
+                           int cap_points, int* n_points, mvo_window_pair* pairs /* may be NULL */, int cap_pairs, int* n_pairs,
+                           int32_t* counts /* 12 */);
 /* ---- keyframe insertion: epipolar inlier filter, triangulation, culling ---- */
 /* geometry::helperTriangulatePoints (src/geometry/motion_estimation.cpp:214-247, called at
  * vo_addFrame.cpp:114-116): pixel2CamNormPlane on the matched pixels of the previous / current keyframe

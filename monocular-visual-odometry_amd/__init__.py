@@ -91,6 +91,23 @@ class MapFuseParams(C.Structure):
 FUSE_OBSERVATION_DTYPE = np.dtype([("frame", np.int32), ("keypoint", np.int32), ("point", np.int32)])
 
 
+class WindowTriangulateParams(C.Structure):
+    """mvo_window_triangulate_params (include/mvo_hip.h)."""
+    _fields_ = [("max_line_px", C.c_double), ("lowe_ratio", C.c_double), ("max_hamming", C.c_int32), ("max_cos_parallax", C.c_double),
+                ("max_reproj_chi2", C.c_double), ("ratio_factor", C.c_double), ("min_baseline", C.c_double)]
+
+
+WINDOW_TRIANGULATE_DEFAULTS = dict(max_line_px=2.0, lowe_ratio=0.8, max_hamming=64, max_cos_parallax=0.9998, max_reproj_chi2=5.991,
+                                   ratio_factor=1.8, min_baseline=0.0)
+# mvo_window_pair, mvo_window_point (include/mvo_hip.h), with the padding the C compiler puts in front of the double
+WINDOW_PAIR_DTYPE = np.dtype([("frame", np.int32), ("keypoint", np.int32), ("train", np.int32), ("hamming", np.int32),
+                              ("status", np.int32), ("p_curr", np.float32, 3), ("p_frame", np.float32, 3), ("cos2", np.float64)],
+                             align=True)
+WINDOW_POINT_DTYPE = np.dtype([("keypoint", np.int32), ("frame", np.int32), ("train", np.int32), ("hamming", np.int32),
+                               ("p_curr", np.float32, 3), ("cos2", np.float64)], align=True)
+assert WINDOW_PAIR_DTYPE.itemsize == 56 and WINDOW_POINT_DTYPE.itemsize == 40
+
+
 class InitPoses(C.Structure):
     """mvo_init_poses (include/mvo_hip.h)."""
     _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
@@ -594,6 +611,53 @@ class Context:
                                         C.byref(n_added), _p(counts)))
         del keep
         return replaced_by, added[:n_added.value].copy(), counts
+
+    # ---- new map points triangulated against every buffered frame (ORB-SLAM's LocalMapping::CreateNewMapPoints)
+    def window_triangulate_search(self, curr, frames, K, max_line_px=2.0, min_baseline=0.0):
+        """mvo_window_triangulate_search: every free keypoint of curr against every free keypoint of every frame along its epipolar
+        line, in one launch -> (idx F x n x 2, dist F x n x 2, n_candidates F x n), per frame the rows of match_knn2_epipolar; a
+        keypoint that is not free, or a frame that fails the baseline test: idx -1, dist INT32_MAX, n_candidates -1.  curr and
+        the frames are dicts as map_fuse takes them; only conn == -1 matters."""
+        if not hasattr(self.lib, "mvo_window_triangulate_search"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_window_triangulate_search")
+        carr, (n,), ckeep = self._fuse_frames([curr])
+        arr, _, keep = self._fuse_frames(frames)
+        F = len(frames)
+        idx, dist, cnt = np.zeros((F, n, 2), np.int32), np.zeros((F, n, 2), np.int32), np.zeros((F, n), np.int32)
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        self._chk(self.lib.mvo_window_triangulate_search(self.h, carr, arr, F, *k, C.c_double(max_line_px), C.c_double(min_baseline),
+                                                         _p(idx), _p(dist), _p(cnt)))
+        del keep, ckeep
+        return idx, dist, cnt
+
+    def window_triangulate(self, curr, frames, K, cap_points=None, cap_pairs=None, **params):
+        """mvo_window_triangulate: the search, the filter, the verification of every pair, the choice -> (points,
+        WINDOW_POINT_DTYPE, sorted by keypoint: one new point per keypoint of curr that has an accepted pair, in the camera of
+        curr; pairs, WINDOW_PAIR_DTYPE, ordered by (frame, train): every pair after the filter with its status; counts 12 int32:
+        free keypoints, active frames, rows with a neighbour, pairs, pairs failing each of the six bits, accepted pairs, new
+        points).  params: the fields of mvo_window_triangulate_params; none given passes NULL (the library's defaults)."""
+        if not hasattr(self.lib, "mvo_window_triangulate"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_window_triangulate")
+        unknown = set(params) - set(WINDOW_TRIANGULATE_DEFAULTS)
+        if unknown:
+            raise TypeError("window_triangulate: unknown parameters %r" % sorted(unknown))
+        carr, (n,), ckeep = self._fuse_frames([curr])
+        arr, counts_kp, keep = self._fuse_frames(frames)
+        P = None
+        if params:
+            d = dict(WINDOW_TRIANGULATE_DEFAULTS, **params)
+            P = C.byref(WindowTriangulateParams(float(d["max_line_px"]), float(d["lowe_ratio"]), int(d["max_hamming"]),
+                                                float(d["max_cos_parallax"]), float(d["max_reproj_chi2"]), float(d["ratio_factor"]),
+                                                float(d["min_baseline"])))
+        capp = n if cap_points is None else int(cap_points)
+        capq = sum(counts_kp) if cap_pairs is None else int(cap_pairs)
+        points, pairs = np.zeros(max(capp, 1), WINDOW_POINT_DTYPE), np.zeros(max(capq, 1), WINDOW_PAIR_DTYPE)
+        n_points, n_pairs, counts = C.c_int(), C.c_int(), np.zeros(12, np.int32)
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        self._chk(self.lib.mvo_window_triangulate(self.h, carr, arr, len(frames), *k, P, _p(points), capp, C.byref(n_points), _p(pairs),
+                                                  capq, C.byref(n_pairs), _p(counts)))
+        del keep, ckeep
+        return points[:n_points.value].copy(), pairs[:n_pairs.value].copy(), counts
 
     def map_debug_get(self, m):
         """mvo_debug_get_map: the resident arrays -> (pos n x 3 f32, desc n x 32)."""

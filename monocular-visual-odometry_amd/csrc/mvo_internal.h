@@ -343,6 +343,38 @@ struct mvo_fuse_state {  // owned by map_fuse_host.cpp, released through mvo_ctx
     DevBuf<int32_t> d_arrive;  // arrival counters, one per (frame, group of 64 map points): self re-arming, zeroed when allocated
 };
 
+// new map points triangulated against every buffered frame (window_triangulate_kernels.hip / window_triangulate_host.cpp;
+// DESIGN.md section 20)
+struct WindowFrame {   // one row of the per-frame table of k_window_epipolar_search and k_window_verify, read from HBM (200 bytes)
+    double F[9];       // mvo_fundamental_from_poses(curr, frame): the line of a keypoint of curr in the frame
+    double R[9], tr[3];  // M = inv(T_w_c_curr) T_w_c_frame: frame coordinates -> coordinates of curr
+    const uint4* d;    // nt x 32 descriptor bytes
+    const double* tg;  // nt x ((double)u, (double)v, tol2), tol2 = -1.0 for a keypoint that is not free
+    int32_t nt, slice; // slice = guided_slice(nt, the launch's train groups)
+    int32_t active;    // the baseline test
+    int32_t pad;
+};
+struct WindowPairIn {  // one pair as k_window_verify reads it (32 bytes)
+    int32_t frame, pad;
+    float uf, vf, uc, vc;  // the keypoint of the frame, the keypoint of curr
+    float sf, sc;          // their scales (1 without scales)
+};
+struct WindowPairOut {  // ... and as it delivers it (40 bytes)
+    float p_curr[3], p_frame[3];
+    double cos2;
+    int32_t status, pad;
+};
+struct WindowVerifyArgs {
+    double fx, fy, cx, cy;
+    double c2max, chi2, rf2;  // max_cos_parallax^2, max_reproj_chi2, ratio_factor^2
+};
+struct mvo_window_state {  // owned by window_triangulate_host.cpp, released through mvo_ctx::window_release
+    DevBuf<uint8_t> d_in;      // one upload per call: the frame table, curr (free flags, pixels, descriptors), the frames' keypoints
+    DevBuf<uint8_t> d_part;    // partial key pairs and counts of guided_knn2(), one block per frame
+    DevBuf<int32_t> d_arrive;  // arrival counters, one per (frame, group of 64 keypoints): self re-arming, zeroed when allocated
+    DevBuf<WindowPairIn> d_pairs;  // the small upload in front of the verification
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -436,6 +468,9 @@ struct mvo_ctx {
     // --- duplicate map points fused over the buffered frames: allocated by the first mvo_map_fuse*, released likewise
     mvo_fuse_state* fuse = nullptr;
     void (*fuse_release)(mvo_ctx*) = nullptr;
+    // --- new map points triangulated against the buffered frames: allocated by the first mvo_window_triangulate*, released likewise
+    mvo_window_state* window = nullptr;
+    void (*window_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -560,6 +595,11 @@ int map_refine_launch(mvo_ctx* ctx, float* d_pos, int n, const MapRefineArgs& a,
 // map_fuse_kernels.hip
 int map_fuse_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, int n_map, const MapFuseArgs& a, const MapFuseFrame* d_frames,
                     int n_frames, int ngroups, const unsigned long long* d_seen, GuidedPartials part, int32_t* out);
+// window_triangulate_kernels.hip
+int window_launch_search(mvo_ctx* ctx, const uint8_t* d_desc, const float* d_xy, const uint8_t* d_free, int nq, const WindowFrame* d_frames,
+                         int n_frames, int ngroups, GuidedPartials part, int32_t* out);
+int window_launch_verify(mvo_ctx* ctx, const WindowPairIn* d_pairs, int n, const WindowFrame* d_frames, const WindowVerifyArgs& a,
+                         WindowPairOut* out);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

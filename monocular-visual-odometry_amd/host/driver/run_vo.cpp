@@ -75,6 +75,19 @@
 // pixels (f32), scales (f32) and connections (int32: map row, -1 free, -2 a point that left the map), UREP = replaced_by (n
 // int32), UADD = the added observations (frame, keypoint, point: n_added x 3 int32), UCNT = the six counts, UIDS = the ids of the
 // map after the call in its new iteration order; and MORD of such a frame stays what its own tracking step saw.
+// Optional key `map_point_create_from_window` (0 / 1, default 0): 1 makes every keyframe insertion while tracking create, right
+// after the reference's own new points and before the culling, a map point for every keypoint of the keyframe that has none and
+// finds a verified partner along its epipolar line in any other buffered frame (my_slam/vo/window_triangulate.h; ORB-SLAM's
+// LocalMapping::CreateNewMapPoints); the reference triangulates against the reference keyframe only
+// (vo_addFrame.cpp:104-116).  Optional keys `map_point_create_max_line_px` (default 2.0), `map_point_create_lowe_ratio` (0.8),
+// `map_point_create_max_hamming` (64), `map_point_create_max_cos_parallax` (0.9998), `map_point_create_min_baseline` (0.0).  With
+// the key on, a keyframe's part of the frame log carries seventeen more records after I3DP: WSET = fx, fy, cx, cy, max_line_px,
+// lowe_ratio, max_hamming, max_cos_parallax, max_reproj_chi2, ratio_factor, min_baseline (f64), WKPN = the keypoints per buffered
+// frame, the keyframe last (int32), WTWC = their poses (n_frames x 16 f64), WDSC / WPIX / WSCL / WCON = frame after frame the
+// descriptors, pixels (f32), scales (f32) and connections (int32: -1 free), WPTS / WPTP / WPTC = the new points (keypoint, frame,
+// train, hamming: n x 4 int32; p_curr: n x 3 f32; cos2: f64), WPRS / WPRP / WPRC = every pair after the filter (frame, keypoint,
+// train, hamming, status: m x 5 int32; p_curr, p_frame: m x 6 f32; cos2: f64), WCNT = the twelve counts, WIDS / WPOS = the ids and
+// world positions (n x 3 f32) of the new map points, WMSZ = the size of the map before and after (2 int32).
 // Optional key `save_frame_log_to`: a binary per-frame record of what the rows produced (keypoints, descriptors, the map's
 // iteration order, inlier matches, keyframe products, pose) for tests/test_gpu_run_vo.py and tests/run_vo_init_body.py,
 // which compose the same run from the oracle and compare stage by stage.  Under `init_from_images` every initialisation
@@ -109,6 +122,8 @@
 #pragma weak mvo_map_refine_positions
 // ... or without the fusion of duplicate map points (`map_point_fuse`): likewise
 #pragma weak mvo_map_fuse
+// ... or without the new map points from the window (`map_point_create_from_window`): likewise
+#pragma weak mvo_window_triangulate
 // ... or without the cell-wise detector (`orb_distribute_keypoints`): likewise
 #pragma weak mvo_orb_distribute_configure
 #pragma weak mvo_calc_keypoints_distributed
@@ -191,6 +206,28 @@ struct FrameLog {
             put("EPIR", T, sizeof T);
         }
         triangulated(fr);
+        if (fr->window_created_) {  // `map_point_create_from_window: 1`: what the call saw and gave
+            vec("WSET", fr->window_setup_);
+            vec("WKPN", fr->window_kp_count_);
+            vec("WTWC", fr->window_T_w_c_);
+            vec("WDSC", fr->window_desc_);
+            vec("WPIX", fr->window_xy_);
+            vec("WSCL", fr->window_scale_);
+            vec("WCON", fr->window_conn_);
+            vec("WPTS", fr->window_points_);
+            vec("WPTP", fr->window_points_p_);
+            vec("WPTC", fr->window_points_cos2_);
+            vec("WPRS", fr->window_pairs_);
+            vec("WPRP", fr->window_pairs_p_);
+            vec("WPRC", fr->window_pairs_cos2_);
+            vec("WCNT", fr->window_counts_);
+            vec("WIDS", fr->window_ids_);
+            vec("WPOS", fr->window_world_);
+            vec("WMSZ", fr->window_map_size_);
+            const vector<int>& c = fr->window_counts_;
+            printf("frame %d: %d new map points from the window (%d free keypoints, %d active frames, %d pairs, %d accepted), map %d -> %d\n",
+                   fr->id_, c[11], c[0], c[1], c[3], c[10], fr->window_map_size_[0], fr->window_map_size_[1]);  // (with or without a log file)
+        }
         mapAfter(map);
         if (fr->fused_) {  // `map_point_fuse: 1`: what the call saw and gave
             vec("USET", fr->fuse_setup_);
@@ -370,6 +407,10 @@ int main(int argc, char** argv) {
         if (vo::mapPointFuse()) {
             if (!mvo_map_fuse) throw std::runtime_error("map_point_fuse: this libmvo_hip.so has no mvo_map_fuse");
             printf("duplicate map points are fused and missed observations added at every keyframe\n");
+        }
+        if (vo::mapPointCreateFromWindow()) {
+            if (!mvo_window_triangulate) throw std::runtime_error("map_point_create_from_window: this libmvo_hip.so has no mvo_window_triangulate");
+            printf("new map points are triangulated against every buffered frame at every keyframe\n");
         }
         if (geometry::orbDistributeKeypoints()) {
             if (!mvo_orb_distribute_configure || !mvo_calc_keypoints_distributed)

@@ -107,6 +107,30 @@ public:
     vector<int> fuse_counts_;
     vector<int> fuse_map_ids_after_;
     bool fused_ = false;
+    // (not in the reference) `map_point_create_from_window: 1`, on the keyframe at whose insertion new map points were made from
+    // every buffered frame (my_slam/vo/window_triangulate.h), what the call saw and gave: the intrinsics and parameters (fx, fy,
+    // cx, cy, max_line_px, lowe_ratio, max_hamming, max_cos_parallax, max_reproj_chi2, ratio_factor, min_baseline), the frames of
+    // frames_buff_ with the keyframe last (keypoints per frame, n_frames x 16 poses, then frame after frame the descriptors,
+    // pixels, scales and connections), the points (keypoint, frame, train, hamming; p_curr; cos2), the pairs (frame, keypoint,
+    // train, hamming, status; p_curr, p_frame; cos2), counts (12), the ids and world positions of the new map points and the
+    // size of the map before and after; empty otherwise
+    vector<double> window_setup_;
+    vector<int> window_kp_count_;
+    vector<double> window_T_w_c_;
+    vector<unsigned char> window_desc_;
+    vector<float> window_xy_, window_scale_;
+    vector<int> window_conn_;
+    vector<int> window_points_;
+    vector<float> window_points_p_;
+    vector<double> window_points_cos2_;
+    vector<int> window_pairs_;
+    vector<float> window_pairs_p_;
+    vector<double> window_pairs_cos2_;
+    vector<int> window_counts_;
+    vector<int> window_ids_;
+    vector<float> window_world_;
+    vector<int> window_map_size_;
+    bool window_created_ = false;
     // (not in the reference) `orb_distribute_keypoints: 1`: per pyramid level, the candidates of calcKeyPoints and the key
     // points it kept (before calcDescriptors drops those near the image border); empty otherwise
     vector<int> distribute_candidates_per_level_;
@@ -163,6 +187,23 @@ public:
         fuse_added_.clear();
         fuse_counts_.clear();
         fuse_map_ids_after_.clear();
+        window_setup_.clear();  // (logged by now; window_created_ stays)
+        window_kp_count_.clear();
+        window_T_w_c_.clear();
+        window_desc_.clear();
+        window_xy_.clear();
+        window_scale_.clear();
+        window_conn_.clear();
+        window_points_.clear();
+        window_points_p_.clear();
+        window_points_cos2_.clear();
+        window_pairs_.clear();
+        window_pairs_p_.clear();
+        window_pairs_cos2_.clear();
+        window_counts_.clear();
+        window_ids_.clear();
+        window_world_.clear();
+        window_map_size_.clear();
     }
     void calcKeyPoints() {
         if (geometry::orbDistributeKeypoints())  // the ORB-SLAM way (my_slam/geometry/orb_distribute.h)

@@ -159,4 +159,6 @@ inline void fuseMapPoints(TrackingState& st, const cv::Mat& K, const Frame::Ptr&
 
 }  // namespace vo
 }  // namespace my_slam
+
+#include "my_slam/vo/window_triangulate.h"  // (declared in tracking_loop.h)
 #endif

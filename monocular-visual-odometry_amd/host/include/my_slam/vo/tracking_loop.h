@@ -51,6 +51,14 @@ inline bool mapPointFuse() {  // the optional key, latched on first use
     return on;
 }
 
+// my_slam/vo/window_triangulate.h (included at the end of map_fuse.h): the new map points of `map_point_create_from_window: 1`
+inline void createMapPointsFromWindow(TrackingState& st, const cv::Mat& K, const Frame::Ptr& curr = nullptr);
+inline bool mapPointCreateFromWindow() {  // the optional key, latched on first use
+    static const bool on =
+        basics::Config::has("map_point_create_from_window") && basics::Config::get<int>("map_point_create_from_window") != 0;
+    return on;
+}
+
 inline cv::Point3f preTranslatePoint3f(const cv::Point3f& p, const cv::Mat& T) {  // opencv_funcs.cpp:67-78
     const double q[4] = {p.x, p.y, p.z, 1};
     double res[3] = {0, 0, 0};
@@ -163,6 +171,7 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
         if (checkLargeMoveForAddKeyFrame(curr, st.ref_)) {
             triangulateWithReferenceKeyframe(curr, st.ref_, K);
             pushCurrPointsToMap(st, curr);
+            if (mapPointCreateFromWindow()) createMapPointsFromWindow(st, K, curr);  // ... and from every other buffered frame
             optimizeMap(st, curr, K);
             if (mapPointFuse()) fuseMapPoints(st, K, curr);  // one point per physical point, every observation in the window
             if (mapPointRefinePositions()) refineMapPointPositions(st, K, curr);  // positions from all observations, poses fixed
