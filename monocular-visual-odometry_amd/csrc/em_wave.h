@@ -181,7 +181,10 @@ PW_FN int real_roots_deg10(EmLds& s, const double (&cin)[11]) {
     PW_LANES(l, kEmLanes) {
         if (l < n_iso) {
             double a = s.ilo[l], b = s.ihi[l];
-            const double fa = horner(s.chain, d, a), fb = horner(s.chain, d, b);
+            double fa = horner(s.chain, d, a);
+            const double fb = horner(s.chain, d, b);
+            // the interval is (a, b]: when a is itself a root, the sign just right of it is the derivative's
+            if (fa == 0) fa = horner(s.chain + 11, d - 1, a);
             int ok = 1;
             double root = 0;
             if (fb == 0) {

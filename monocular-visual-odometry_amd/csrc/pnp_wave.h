@@ -967,10 +967,13 @@ PW_FN void rodrigues_fwd(const double (&r)[3], double (&R)[9], double (&J)[27], 
                                  rz,      0,  rz, 0,  0,       0,  rx, 0,  0,  ry, rx, ry, rz + rz};
         const double d_r_x[27] = {0, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0};
         const double rr[3] = {rx, ry, rz};
+        // (1 - cos theta) / theta: c1 above is accurate to eps absolutely, which is all R needs, but the quotient would
+        // carry eps / theta into the derivative (4e-9 at theta = 1e-8); the half-angle form does not cancel
+        const double sh = sin(0.5 * theta), c1j = 2 * sh * sh;
         PW_UNROLL
         for (int i = 0; i < 3; i++) {
             const double ri = rr[i];
-            const double a0 = -s * ri, a1 = (s - 2 * c1 * itheta) * ri, a2 = c1 * itheta, a3 = (c - s * itheta) * ri,
+            const double a0 = -s * ri, a1 = (s - 2 * c1j * itheta) * ri, a2 = c1j * itheta, a3 = (c - s * itheta) * ri,
                          a4 = s * itheta;
             PW_UNROLL
             for (int k = 0; k < 9; k++)

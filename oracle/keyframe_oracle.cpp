@@ -195,7 +195,10 @@ int real_roots_deg10(const double* cin, double* roots) {
     int nr = 0;
     for (int q = 0; q < n_iso; q++) {
         double a = ilo[q], b = ihi[q];
-        const double fa = horner(s.c[0], d, a), fb = horner(s.c[0], d, b);
+        double fa = horner(s.c[0], d, a);
+        const double fb = horner(s.c[0], d, b);
+        // the interval is (a, b]: when a is itself a root, the sign just right of it is the derivative's
+        if (fa == 0) fa = horner(s.c[1], d - 1, a);
         if (fb == 0) {
             roots[nr++] = b;
             continue;

@@ -398,9 +398,11 @@ void rodrigues_fwd(const double r[3], double R[9], double* J /* 3 x 9 or null */
                                  rz,      0,  rz, 0,  0,       0,  rx, 0,  0,  ry, rx, ry, rz + rz};
         const double d_r_x[27] = {0, 0, 0, 0, 0, -1, 0, 1, 0, 0, 0, 1, 0, 0, 0, -1, 0, 0, 0, -1, 0, 1, 0, 0, 0, 0, 0};
         const double rr[3] = {rx, ry, rz};
+        // (1 - cos theta) / theta without the cancellation, as csrc/pnp_wave.h: only the derivative needs it
+        const double sh = sin(0.5 * theta), c1j = 2 * sh * sh;
         for (int i = 0; i < 3; i++) {
             const double ri = rr[i];
-            const double a0 = -s * ri, a1 = (s - 2 * c1 * itheta) * ri, a2 = c1 * itheta, a3 = (c - s * itheta) * ri,
+            const double a0 = -s * ri, a1 = (s - 2 * c1j * itheta) * ri, a2 = c1j * itheta, a3 = (c - s * itheta) * ri,
                          a4 = s * itheta;
             for (int k = 0; k < 9; k++)
                 J[i * 9 + k] = a0 * I[k] + a1 * rrt[k] + a2 * drrt[i * 9 + k] + a3 * r_x[k] + a4 * d_r_x[i * 9 + k];
