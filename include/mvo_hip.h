@@ -423,6 +423,53 @@ int mvo_map_size(mvo_ctx* ctx, mvo_map* map, int* n);
  * mvo_invert_pose, each product summed k = 0..3 in order, no re-orthonormalisation).  T_w_c_prev2 NULL: T_pred = T_prev.
  * MVO_ERR_INVALID for a singular T_prev2. */
 int mvo_predict_pose(const double* T_w_c_prev2 /* or NULL */, const double* T_w_c_prev, double* T_w_c_pred);
+/* The reference's poseEstimationPnP_ (vo.cpp:291-347) runs cv::solvePnPRansac from minimal subsets even when every match already
+ * lies within a few pixels of a predicted pose, and its optimizeSingleFrame (g2o_ba.cpp:34-170, called at vo.cpp:466) has no
+ * outlier rounds.  ORB-SLAM's TrackWithMotionModel instead calls Optimizer::PoseOptimization: a robust motion-only optimisation
+ * from the predicted pose over all matches, inliers and outliers classified in four rounds.  This is that step, declared
+ * operation by operation in DESIGN.md section 21, f64, every operation one IEEE operation in the written order:
+ *   state     (R, t) = rows 0..2 of T_c_w; T_c_w^0 = mvo_invert_pose(T_w_c_init)
+ *   q_r       ((R_r0 P_x + R_r1 P_y) + R_r2 P_z) + t_r, P = (double)pts3d[k];  u = (fx q_x) / q_z + cx, v likewise
+ *   e, c      (u - (double)uv_x, v - (double)uv_y);  c = (e_x e_x + e_y e_y) s_k, s_k = (double)inv_sigma2[k] or 1.0
+ *   rho, w    c <= d d ? c : (2 d) sqrt(c) - d d;  c <= d d ? 1 : d / sqrt(c), d = huber_delta; without the kernel c and 1
+ *   J         A [-[q]x | I] for the left update q' = q + w x q + v, A the 2 x 3 derivative of the projection
+ *   sums      H = sum (w s_k) J^T J (21), b = sum (w s_k) J^T e (6), chi2 = sum rho: slot k mod 256 adds its observations in
+ *             ascending k from 0.0, then eight times S <- S[even] + S[odd]
+ *   trial     lambda = 1e-3 max diag H at the start of a round; (H + lambda I) delta = -b by 6 x 6 Cholesky; W = Rodrigues(omega),
+ *             R' = W R, t' = W t + upsilon; accepted if every participating observation has q_z > 0 at the new state and
+ *             chi2' < chi2: the state moves, lambda *= 0.1, the round ends when chi2 - chi2' <= rel_tolerance chi2; otherwise
+ *             lambda *= 10; at most `iterations` trials per round
+ *   rounds    each starts again from T_c_w^0 with the current inlier set, the kernel on except in the last of >= 2 rounds; after
+ *             a round every observation is classified at its final state: outlier = !(q_z > 0) || c > chi2_threshold; an
+ *             observation with !(q_z > 0) at the initial pose never takes part and is always an outlier; fewer than min_inliers
+ *             left stops the loop
+ * info = (status, rounds run, trials, accepted steps, inliers, observations in front at the start).  Status 0: optimised;
+ * 1: the inliers fell below min_inliers, the pose of that round is still reported; 2: fewer than min_inliers observations in
+ * front at the start (or n == 0, without a launch): the pose is the initial one, bit for bit, every flag 1, chi2 (0, 0); 3: no
+ * trial was accepted in any round: the pose is the initial one, bit for bit, the flags are the classification at it.
+ * chi2 = (start of round 0, end of the last round run).  T_c_w is the final state of the last round run (last row 0 0 0 1),
+ * T_w_c = mvo_invert_pose(T_c_w).
+ * MVO_ERR_INVALID: a null pointer with a positive count, a singular or non-finite pose, fx or fy 0 or intrinsics not finite, a
+ * non-finite pts3d or pts2d, an inv_sigma2 entry that is negative or not finite, params out of range.  MVO_ERR_CAPACITY:
+ * n > 4096.  In every error case nothing is written. */
+typedef struct {
+    int32_t rounds;          /* 1..8,  default 4 */
+    int32_t iterations;      /* 1..64, default 10: LM trials per round */
+    int32_t min_inliers;     /* 6..4096, default 10 */
+    double chi2_threshold;   /* > 0, finite; default 5.991 */
+    double huber_delta;      /* > 0, finite; default sqrt(5.991) */
+    double rel_tolerance;    /* >= 0, finite; default 1e-6 */
+} mvo_pose_optimize_params;  /* NULL = defaults */
+/* ORB-SLAM Optimizer::PoseOptimization in place of cv::solvePnPRansac at vo.cpp:291-347 when the matches come from a predicted
+ * pose.  One upload, one launch (k_pose_optimize: one workgroup runs every round, trial and classification), one wait. */
+int mvo_optimize_pose(mvo_ctx* ctx, const float* pts3d /* n x 3, world */, const float* pts2d /* n x 2 */,
+                      const float* inv_sigma2 /* n or NULL = 1 */, int n, const double* T_w_c_init, double fx, double fy,
+                      double cx, double cy, const mvo_pose_optimize_params* params, double* T_w_c /* 16 */,
+                      double* T_c_w /* 16, may be NULL */, uint8_t* outlier /* n */, double* chi2 /* 2 */, int32_t* info /* 6 */);
+/* The rounds of the last mvo_optimize_pose of this ctx that launched, for localising a parity failure: one row of 6 doubles per
+ * round run (inliers going in, chi2 at the start, chi2 at the end, trials, accepted steps, inliers coming out); *n_rounds is
+ * set; MVO_ERR_CAPACITY if cap < *n_rounds, MVO_ERR_STATE before the first such call. */
+int mvo_debug_get_pose_optimize(mvo_ctx* ctx, double* rows /* cap x 6 */, int cap, int* n_rounds);
 /* ---- map points refreshed from their observations --------------------------------------------- */
 /* The reference gives a map point the descriptor and the viewing direction of the ONE frame that created it
  * (pushCurrPointsToMap_, vo.cpp:528-576) and never writes them again; ORB-SLAM, whose matching the calls above follow, keeps a

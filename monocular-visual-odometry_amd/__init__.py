@@ -108,6 +108,12 @@ WINDOW_POINT_DTYPE = np.dtype([("keypoint", np.int32), ("frame", np.int32), ("tr
 assert WINDOW_PAIR_DTYPE.itemsize == 56 and WINDOW_POINT_DTYPE.itemsize == 40
 
 
+class PoseOptimizeParams(C.Structure):
+    """mvo_pose_optimize_params (include/mvo_hip.h)."""
+    _fields_ = [("rounds", C.c_int32), ("iterations", C.c_int32), ("min_inliers", C.c_int32), ("chi2_threshold", C.c_double),
+                ("huber_delta", C.c_double), ("rel_tolerance", C.c_double)]
+
+
 class InitPoses(C.Structure):
     """mvo_init_poses (include/mvo_hip.h)."""
     _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
@@ -667,6 +673,46 @@ class Context:
         self._chk(self.lib.mvo_debug_get_map(self.h, m, _p(pos), _p(desc), n, C.byref(cnt)))
         assert cnt.value == n
         return pos, desc
+
+    def optimize_pose(self, pts3d, pts2d, T_w_c_init, K, inv_sigma2=None, rounds=None, iterations=None, min_inliers=None,
+                      chi2_threshold=None, huber_delta=None, rel_tolerance=None):
+        """mvo_optimize_pose: the pose from a robust motion-only Levenberg-Marquardt over all matches, from the predicted pose
+        T_w_c_init (ORB-SLAM's PoseOptimization; one launch) -> (T_w_c 4 x 4, T_c_w 4 x 4, outlier n uint8, chi2 2 f64: start of
+        round 0, end of the last round; info 6 int32: status, rounds run, trials, accepted steps, inliers, observations in front
+        at the start).  Status 0: optimised, 1: the inliers fell below min_inliers, 2: too few observations in front at the
+        start, 3: no trial accepted.  pts3d: n x 3 world, pts2d: n x 2 pixels, inv_sigma2: n weights or None.  The keyword
+        arguments default to the library's (4, 10, 10, 5.991, sqrt(5.991), 1e-6)."""
+        if not hasattr(self.lib, "mvo_optimize_pose"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_optimize_pose")
+        p3 = np.ascontiguousarray(pts3d, np.float32).reshape(-1, 3)
+        p2 = np.ascontiguousarray(pts2d, np.float32).reshape(-1, 2)
+        if len(p3) != len(p2):
+            raise ValueError("one pixel per point")
+        sg = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1)
+        if sg is not None and len(sg) != len(p3):
+            raise ValueError("one weight per observation")
+        T0 = np.ascontiguousarray(T_w_c_init, np.float64).reshape(16)
+        given = (rounds, iterations, min_inliers, chi2_threshold, huber_delta, rel_tolerance)
+        params = None
+        if any(v is not None for v in given):
+            dflt = (4, 10, 10, 5.991, float(np.sqrt(np.float64(5.991))), 1e-6)
+            v = [d if g is None else g for g, d in zip(given, dflt)]
+            params = PoseOptimizeParams(int(v[0]), int(v[1]), int(v[2]), float(v[3]), float(v[4]), float(v[5]))
+            params = C.byref(params)
+        n = len(p3)
+        Twc, Tcw, outlier = np.zeros((4, 4), np.float64), np.zeros((4, 4), np.float64), np.zeros(n, np.uint8)
+        chi2, info = np.zeros(2, np.float64), np.zeros(6, np.int32)
+        k = [C.c_double(K[name]) for name in ("fx", "fy", "cx", "cy")]
+        self._chk(self.lib.mvo_optimize_pose(self.h, _p(p3), _p(p2), None if sg is None else _p(sg), n, _p(T0), *k, params, _p(Twc),
+                                             _p(Tcw), _p(outlier), _p(chi2), _p(info)))
+        return Twc, Tcw, outlier, chi2, info
+
+    def pose_optimize_debug_get(self):
+        """mvo_debug_get_pose_optimize: one row per round of the last mvo_optimize_pose that launched -> rounds x 6 f64 (inliers
+        going in, chi2 at the start, chi2 at the end, trials, accepted steps, inliers coming out)."""
+        rows, cnt = np.zeros((8, 6), np.float64), C.c_int()
+        self._chk(self.lib.mvo_debug_get_pose_optimize(self.h, _p(rows), 8, C.byref(cnt)))
+        return rows[:cnt.value].copy()
 
     # ---- bundle adjustment
     def _ba_problem(self, poses, points, edge_pose, edge_point, edge_uv, focal, cx, cy, info, huber_delta,

@@ -189,6 +189,7 @@ void mvo_destroy(mvo_ctx* ctx) {
     if (ctx->refine_release) ctx->refine_release(ctx);
     if (ctx->fuse_release) ctx->fuse_release(ctx);
     if (ctx->window_release) ctx->window_release(ctx);
+    if (ctx->pose_opt_release) ctx->pose_opt_release(ctx);
     ba_pool_release(ctx);
     ctx->d_img.release(), ctx->d_mq.release(), ctx->d_mt.release(), ctx->d_mqxy.release(), ctx->d_mtxy.release(), ctx->d_mout.release();
     void* dev[] = {ctx->d_raw, ctx->d_blur, ctx->d_tabs, ctx->d_pyr_regs, ctx->d_kp, ctx->d_desc_buf, ctx->d_fh_slots, ctx->d_fh_line, ctx->d_fh_arrive};

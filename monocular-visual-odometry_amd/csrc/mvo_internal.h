@@ -375,6 +375,28 @@ struct mvo_window_state {  // owned by window_triangulate_host.cpp, released thr
     DevBuf<WindowPairIn> d_pairs;  // the small upload in front of the verification
 };
 
+// the per-frame pose from a robust motion-only optimisation (pose_optimize_kernels.hip / pose_optimize_host.cpp)
+#define PO_MAX_OBS 4096  // observations per call: 24 bytes each in LDS, 16 per lane
+#define PO_MAX_ROUNDS 8
+struct PoseOptArgs {
+    double T0[12];  // rows 0..2 of T_c_w^0
+    double fx, fy, cx, cy;
+    double delta, chi2_thr, rel_tol;  // huber_delta, chi2_threshold, rel_tolerance
+    int32_t rounds, iterations, min_inliers, has_sigma;
+};
+struct PoseOptOut {  // what k_pose_optimize writes into the ctx's pinned staging, the n flags behind it
+    double Tcw[12];
+    double chi2[2];
+    double rows[PO_MAX_ROUNDS * 6];
+    int32_t info[6];
+    int32_t pad[2];
+};
+struct mvo_pose_opt_state {  // owned by pose_optimize_host.cpp, released through mvo_ctx::pose_opt_release
+    DevBuf<uint8_t> d_in;    // one upload per call: pts3d, pts2d, inv_sigma2
+    int n_rounds = 0;        // rows of the last call that launched (mvo_debug_get_pose_optimize)
+    double rows[PO_MAX_ROUNDS * 6] = {0};
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -471,6 +493,9 @@ struct mvo_ctx {
     // --- new map points triangulated against the buffered frames: allocated by the first mvo_window_triangulate*, released likewise
     mvo_window_state* window = nullptr;
     void (*window_release)(mvo_ctx*) = nullptr;
+    // --- the pose from a robust motion-only optimisation: allocated by the first mvo_optimize_pose, released likewise
+    mvo_pose_opt_state* pose_opt = nullptr;
+    void (*pose_opt_release)(mvo_ctx*) = nullptr;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -600,6 +625,9 @@ int window_launch_search(mvo_ctx* ctx, const uint8_t* d_desc, const float* d_xy,
                          int n_frames, int ngroups, GuidedPartials part, int32_t* out);
 int window_launch_verify(mvo_ctx* ctx, const WindowPairIn* d_pairs, int n, const WindowFrame* d_frames, const WindowVerifyArgs& a,
                          WindowPairOut* out);
+// pose_optimize_kernels.hip
+int pose_optimize_launch(mvo_ctx* ctx, const float* d_p3, const float* d_p2, const float* d_s, int n, const PoseOptArgs& a, PoseOptOut* out,
+                         uint8_t* out_outlier);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

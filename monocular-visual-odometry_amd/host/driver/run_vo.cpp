@@ -40,6 +40,17 @@
 // records after MORD: PRVP = the 32 f64 of T_prev2 and T_prev as used (T_prev twice without a prev2), PRED = the 16 f64 of
 // the predicted pose, PPOS / PDSC = the map's positions (n x 3 f32) and descriptors (n x 32) as uploaded, in MORD order,
 // MPRJ = the matches handed to PnP before the inlier selection (queryIdx -> index among the points in view).
+// Optional key `tracking_pose_by_optimization` (0 / 1, default 0; requires `tracking_match_by_projection: 1`, run_vo ends with an
+// error that says so otherwise): 1 makes every tracked frame with at least min_inliers matches take its pose from a robust
+// motion-only optimisation from the predicted pose over all the matches (my_slam/vo/pose_optimization.h; ORB-SLAM's
+// Optimizer::PoseOptimization) instead of solvePnPRansac (vo.cpp:326-329): its non-outliers stand in for the
+// PnP inliers, its pose for invT(convertRt2T(R, t)); a frame whose optimisation ends with a status other than 0 falls back to
+// solvePnPRansac exactly as without the key.  Optional keys `pose_optimization_rounds` (default 4), `pose_optimization_iterations`
+// (10), `pose_optimization_min_inliers` (10), `pose_optimization_chi2_threshold` (5.991).  With the key on, a tracked frame's part
+// of the frame log carries after MPRJ, if the optimisation was called: OSET = fx, fy, cx, cy, rounds, iterations, min_inliers,
+// chi2_threshold, huber_delta, rel_tolerance (f64), OINI = the initial pose (16 f64), OP3D / OP2D / OSIG = the matches' map
+// points (n x 3 f32), pixels (n x 2 f32) and inv_sigma2 (n f32), OTWC / OTCW = the result (16 f64 each), OINF = info (6 int32),
+// OCHI = chi2 (2 f64), OOUT = the outlier flags (n); and always OFBK = int32, 1 if the frame fell back.
 // Optional key `orb_distribute_keypoints` (0 / 1, default 0): 1 makes Frame::calcKeyPoints extract the ORB-SLAM way -- FAST cell by
 // cell with two thresholds, a quadtree spread per level (my_slam/geometry/orb_distribute.h; the reference's README.md section 5)
 // -- instead of cv::ORB::detect (feature_match.cpp:22-23).  Its four parameters, optional as well: `orb_distribute_ini_threshold`
@@ -116,6 +127,8 @@
 // ... or without tracking by projection (`tracking_match_by_projection`): likewise
 #pragma weak mvo_predict_pose
 #pragma weak mvo_map_match_features_projection
+// ... or without the pose optimisation (`tracking_pose_by_optimization`): likewise
+#pragma weak mvo_optimize_pose
 // ... or without the map-point refresh (`map_point_refresh`): likewise
 #pragma weak mvo_map_refresh
 // ... or without the position refinement (`map_point_refine_positions`): likewise
@@ -188,6 +201,21 @@ struct FrameLog {
             vec("PPOS", fr->projection_map_pos_);
             vec("PDSC", fr->projection_map_desc_);
             vec("MPRJ", fr->projection_matches_);
+        }
+        if (fr->pose_opt_fallback_ >= 0) {  // `tracking_pose_by_optimization: 1`: what the call saw and gave, if it was made
+            if (!fr->pose_opt_setup_.empty()) {
+                vec("OSET", fr->pose_opt_setup_);
+                vec("OINI", fr->pose_opt_init_);
+                vec("OP3D", fr->pose_opt_p3_);
+                vec("OP2D", fr->pose_opt_p2_);
+                vec("OSIG", fr->pose_opt_sigma_);
+                vec("OTWC", fr->pose_opt_T_w_c_);
+                vec("OTCW", fr->pose_opt_T_c_w_);
+                vec("OINF", fr->pose_opt_info_);
+                vec("OCHI", fr->pose_opt_chi2_);
+                vec("OOUT", fr->pose_opt_outlier_);
+            }
+            put("OFBK", &fr->pose_opt_fallback_, sizeof(int));
         }
         vec("MMAP", fr->matches_with_map_);  // the PnP inliers' matches (vo.cpp:336-349)
         const int flags[2] = {good ? 1 : 0, is_keyframe ? 1 : 0};
@@ -394,6 +422,12 @@ int main(int argc, char** argv) {
             if (!mvo_predict_pose || !mvo_map_match_features_projection)
                 throw std::runtime_error("tracking_match_by_projection: this libmvo_hip.so has no mvo_map_match_features_projection");
             printf("frames are tracked by projection of the map with a predicted pose\n");
+        }
+        if (vo::trackingPoseByOptimization()) {
+            if (!vo::trackingMatchByProjection())
+                throw std::runtime_error("tracking_pose_by_optimization requires tracking_match_by_projection: 1");
+            if (!mvo_optimize_pose) throw std::runtime_error("tracking_pose_by_optimization: this libmvo_hip.so has no mvo_optimize_pose");
+            printf("tracked frames take their pose from a robust optimisation over all matches\n");
         }
         if (vo::mapPointRefresh()) {
             if (!mvo_map_refresh) throw std::runtime_error("map_point_refresh: this libmvo_hip.so has no mvo_map_refresh");

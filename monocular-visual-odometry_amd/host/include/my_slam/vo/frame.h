@@ -55,6 +55,16 @@ public:
     vector<float> projection_map_pos_;
     vector<unsigned char> projection_map_desc_;
     vector<cv::DMatch> projection_matches_;
+    // (not in the reference) `tracking_pose_by_optimization: 1`: whether the frame fell back to solvePnPRansac (-1: the step was
+    // not reached) and, if the optimisation was called (my_slam/vo/pose_optimization.h), what it saw and gave: the intrinsics and
+    // parameters (fx, fy, cx, cy, rounds, iterations, min_inliers, chi2_threshold, huber_delta, rel_tolerance), the predicted pose
+    // (16), the matches' map points (n x 3), pixels (n x 2) and inv_sigma2 (n), T_w_c and T_c_w (16 each), info (6), chi2 (2), the
+    // outlier flags (n); empty otherwise
+    int pose_opt_fallback_ = -1;
+    vector<double> pose_opt_setup_, pose_opt_init_, pose_opt_T_w_c_, pose_opt_T_c_w_, pose_opt_chi2_;
+    vector<float> pose_opt_p3_, pose_opt_p2_, pose_opt_sigma_;
+    vector<int> pose_opt_info_;
+    vector<unsigned char> pose_opt_outlier_;
     // (not in the reference) `map_point_refresh: 1`, on the keyframe after whose insertion the map points were refreshed
     // (my_slam/vo/map_refresh.h): the ids of MapOnDevice::order() as the frame's own tracking step saw it (the refresh re-reads
     // the map), then in the order of the refreshed map: the observation starts (n + 1), the observations' descriptors

@@ -168,6 +168,12 @@ inline bool trackingMatchByProjection() {  // the optional key, latched on first
     return on;
 }
 
+// my_slam/vo/pose_optimization.h (included at the end of this header): the pose of `tracking_pose_by_optimization: 1`
+inline bool trackingPoseByOptimization();
+inline int poseOptimizationMinInliers();
+inline int optimizePoseFromMatches(const Frame::Ptr& curr, const vector<cv::Point3f>& pts_3d, const vector<cv::Point2f>& pts_2d,
+                                   const cv::Mat& K, vector<int>& inliers, cv::Mat& T_w_c);
+
 // VisualOdometry::poseEstimationPnP_ (vo.cpp:270-383): matches the map points in view against the frame, solves
 // PnP with RANSAC, records the inlier connections and sets curr->T_w_c_.  Returns is_pnp_good.
 inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const Frame::Ptr& curr, const Frame::Ptr& prev,
@@ -202,10 +208,22 @@ inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const F
     bool is_pnp_good = num_matches >= kMinPtsForPnP;
     if (is_pnp_good) {
         vector<int> pnp_inliers;
-        cv::Mat R_vec, t, R;
-        const bool found = geometry::solvePnPRansac(pts_3d, pts_2d, K, R_vec, t, 100, 2.0f, 0.999, pnp_inliers);
-        if (!found) throw std::runtime_error("solvePnPRansac found no pose (cv::Rodrigues would throw on the empty rvec)");
-        geometry::Rodrigues(R_vec, R);
+        cv::Mat R_vec, t, R, T_w_c_optimised;
+        bool optimised = false;
+        if (trackingPoseByOptimization()) {
+            // curr->T_w_c_ is still the predicted pose: a robust motion-only optimisation from it over all the matches; its
+            // non-outliers stand in for the PnP inliers, its pose for invT(convertRt2T(R, t)); any status but 0 falls back
+            if (!trackingMatchByProjection())
+                throw std::runtime_error("tracking_pose_by_optimization requires tracking_match_by_projection: 1");
+            if (num_matches >= poseOptimizationMinInliers())
+                optimised = optimizePoseFromMatches(curr, pts_3d, pts_2d, K, pnp_inliers, T_w_c_optimised) == 0;
+            curr->pose_opt_fallback_ = optimised ? 0 : 1;
+        }
+        if (!optimised) {
+            const bool found = geometry::solvePnPRansac(pts_3d, pts_2d, K, R_vec, t, 100, 2.0f, 0.999, pnp_inliers);
+            if (!found) throw std::runtime_error("solvePnPRansac found no pose (cv::Rodrigues would throw on the empty rvec)");
+            geometry::Rodrigues(R_vec, R);
+        }
         vector<cv::DMatch> tmp_matches_with_map;
         for (int good_idx : pnp_inliers) {
             const cv::DMatch& match = curr->matches_with_map_[good_idx];
@@ -215,7 +233,7 @@ inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const F
             curr->inliers_to_mappt_connections_[match.trainIdx] = PtConn{-1, inlier_mappoint->id_};
         }
         curr->matches_with_map_.swap(tmp_matches_with_map);
-        curr->T_w_c_ = basics::invT(basics::convertRt2T(R, t));
+        curr->T_w_c_ = optimised ? T_w_c_optimised : basics::invT(basics::convertRt2T(R, t));
         double d2 = 0;  // basics::calcMatNorm(t_curr - t_prev), vo.cpp:352-356
         for (int i = 0; i < 3; ++i) {
             const double d = curr->T_w_c_.at<double>(i, 3) - prev->T_w_c_.at<double>(i, 3);
@@ -231,6 +249,7 @@ inline bool poseEstimationPnP(MapOnDevice& dev_map, const Map::Ptr& map, const F
 }  // namespace my_slam
 
 #include "my_slam/vo/projection_match.h"
+#include "my_slam/vo/pose_optimization.h"
 
 #ifndef MVO_HAVE_OPENCV
 namespace cv {
