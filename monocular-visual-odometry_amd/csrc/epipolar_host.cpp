@@ -1,8 +1,7 @@
 // csrc/epipolar_host.cpp -- host side of the pose-guided matcher (include/mvo_hip.h: mvo_match_knn2_epipolar,
 // mvo_match_knn2_epipolar_dev, mvo_match_features_epipolar, mvo_fundamental_from_poses): argument checks, the per-train
 // tolerance, staging, the filter and the one-query-per-train rule.  The kernel is in epipolar_kernels.hip, the arithmetic in
-// DESIGN.md section 14.  No other translation unit refers to this one: mvo_destroy reaches epipolar_release through
-// mvo_ctx::epi_release.
+// DESIGN.md section 14.  No other translation unit refers to this one.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -13,17 +12,8 @@
 
 namespace {
 
-void epipolar_release(mvo_ctx* ctx) {
-    delete ctx->epi;
-    ctx->epi = nullptr;
-}
-
 int ensure_bufs(mvo_ctx* ctx, int nq, int nt) {
-    if (!ctx->epi) {
-        ctx->epi = new mvo_epipolar_state();
-        ctx->epi_release = epipolar_release;
-    }
-    mvo_epipolar_state* e = ctx->epi;
+    mvo_epipolar_state* e = mvo_state(ctx->epi);
     int r;
     if ((r = e->d_q.ensure(ctx, (size_t)nq * 32, 4096 * 32)) || (r = e->d_qxy.ensure(ctx, (size_t)nq * 2, 4096 * 2)) ||
         (r = e->scratch.ensure(ctx, nq)) || (r = e->d_t.ensure(ctx, (size_t)nt * 32, 4096 * 32)) ||
@@ -57,7 +47,7 @@ int check_and_trivial(mvo_ctx* ctx, const void* q, const float* qxy, int nq, con
 // d_q / d_t: device descriptors; qxy, txy, t_scale: host.  nq, nt >= 1, arguments checked.
 int run(mvo_ctx* ctx, const uint8_t* d_q, const float* qxy, int nq, const uint8_t* d_t, const float* txy, const float* t_scale,
         int nt, const double* F, double max_line_px, int32_t* idx, int32_t* dist, int32_t* n_candidates) {
-    mvo_epipolar_state* e = ctx->epi;
+    mvo_epipolar_state* e = ctx->epi.get();
     std::vector<double> tol2(nt);
     for (int j = 0; j < nt; ++j) tol2[j] = guided_tol2(max_line_px, t_scale, j);
     EpipolarArgs a;
@@ -70,11 +60,9 @@ int run(mvo_ctx* ctx, const uint8_t* d_q, const float* qxy, int nq, const uint8_
     MVO_HIP(hipMemcpyAsync(e->d_tol2, tol2.data(), (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
     ExtractGate gate(ctx);
     if ((r = epipolar_launch_knn2(ctx, d_q, e->d_qxy, nq, d_t, e->d_txy, e->d_tol2, nt, a, e->scratch.partials(),
-                                  reinterpret_cast<int32_t*>(ctx->h_pin))))
+                                  reinterpret_cast<int32_t*>(ctx->h_pin))) ||
+        (r = StagedCall{ctx}.finish(gate)))  // (tol2 is pageable: its copy has left the vector by now either way)
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (tol2 is pageable: its copy has left the vector by now either way)
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     std::memcpy(idx, ctx->h_pin, (size_t)nq * 8);
     std::memcpy(dist, ctx->h_pin + (size_t)nq * 8, (size_t)nq * 8);
     if (n_candidates) std::memcpy(n_candidates, ctx->h_pin + (size_t)nq * 16, (size_t)nq * 4);
@@ -95,7 +83,7 @@ int mvo_match_knn2_epipolar(mvo_ctx* ctx, const uint8_t* q, const float* qxy, in
     if (r || done) return r;
     MVO_HIP(hipSetDevice(ctx->device));
     if ((r = ensure_bufs(ctx, nq, nt))) return r;
-    mvo_epipolar_state* e = ctx->epi;
+    mvo_epipolar_state* e = ctx->epi.get();
     MVO_HIP(hipMemcpyAsync(e->d_q, q, (size_t)nq * 32, hipMemcpyHostToDevice, ctx->stream));
     MVO_HIP(hipMemcpyAsync(e->d_t, t, (size_t)nt * 32, hipMemcpyHostToDevice, ctx->stream));
     return run(ctx, e->d_q, qxy, nq, e->d_t, txy, t_scale, nt, F, max_line_px, idx, dist, n_candidates);

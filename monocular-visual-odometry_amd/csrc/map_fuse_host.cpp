@@ -1,8 +1,7 @@
 // csrc/map_fuse_host.cpp -- host side of the fusion of duplicate map points (include/mvo_hip.h: mvo_map_fuse_search,
 // mvo_map_fuse): argument checks, the seen masks, the pose inverses, one upload, the launch, the results, and the serial
 // resolution (one claimant per keypoint, union-find merges, additions, survivors).  The kernel is in map_fuse_kernels.hip,
-// the rule in DESIGN.md section 19.  No other translation unit refers to this one: mvo_destroy reaches fuse_release through
-// mvo_ctx::fuse_release.
+// the rule in DESIGN.md section 19.  No other translation unit refers to this one.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -10,31 +9,9 @@
 #include <string>
 #include <vector>
 
-#include "guided_knn2.h"
+#include "guided_match_host.h"
 
 namespace {
-
-void fuse_release(mvo_ctx* ctx) {
-    delete ctx->fuse;
-    ctx->fuse = nullptr;
-}
-
-inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
-
-int ensure_bufs(mvo_ctx* ctx, size_t in_bytes, size_t part_bytes, size_t n_arrive) {
-    if (!ctx->fuse) {
-        ctx->fuse = new mvo_fuse_state();
-        ctx->fuse_release = fuse_release;
-    }
-    mvo_fuse_state* e = ctx->fuse;
-    int r;
-    if ((r = e->d_in.ensure(ctx, in_bytes, (size_t)1 << 20)) || (r = e->d_part.ensure(ctx, part_bytes, (size_t)1 << 18))) return r;
-    const size_t had = e->d_arrive.cap;
-    if ((r = e->d_arrive.ensure(ctx, n_arrive, 4096))) return r;
-    if (e->d_arrive.cap != had)  // the counters re-arm themselves: zeroed once per allocation
-        MVO_HIP(hipMemsetAsync(e->d_arrive, 0, e->d_arrive.cap * sizeof(int32_t), ctx->stream));
-    return MVO_OK;
-}
 
 // The checks, the upload, the launch, the wait.  On success the raw results lie in ctx->h_pin: idx, dist, px, n_candidates,
 // n_frames blocks of n_map rows each; seen receives the masks.  *launched is false when there was nothing to search.
@@ -57,72 +34,53 @@ int search(mvo_ctx* ctx, mvo_map* map, const mvo_fuse_frame* frames, int n_frame
     int nt_max = 0;
     for (int f = 0; f < n_frames; ++f) {
         const mvo_fuse_frame& F = frames[f];
-        if (F.n < 0 || (F.n && (!F.desc || !F.xy || !F.conn))) return fail("bad arguments");
-        if (F.n > 65535) return fail("a frame with more than 65535 keypoints", MVO_ERR_CAPACITY);
-        for (int k = 0; k < 16; ++k)
-            if (!std::isfinite(F.T_w_c[k])) return fail("T_w_c is not finite");
         double Ti[16];
-        if (mvo_invert_pose(F.T_w_c, Ti) != MVO_OK) return fail("T_w_c is singular");
-        std::memcpy(&Tcw[12 * (size_t)f], Ti, 12 * sizeof(double));
-        for (int j = 0; j < F.n; ++j) {
+        auto conn_and_seen = [&](int j) -> int {
             if (F.conn[j] < -2 || F.conn[j] >= n_map) return fail("conn outside [-2, n_map)");
-            if (F.scale && (!std::isfinite(F.scale[j]) || F.scale[j] < 0)) return fail("scale entry negative or not finite");
             if (F.conn[j] >= 0) seen[F.conn[j]] |= 1ull << f;
-        }
+            return MVO_OK;
+        };
+        if (int r = guided_check_frame(F, Ti, fail, conn_and_seen)) return r;
+        std::memcpy(&Tcw[12 * (size_t)f], Ti, 12 * sizeof(double));
         total += (size_t)F.n;
         nt_max = std::max(nt_max, (int)F.n);
     }
     if (n_map == 0 || n_frames == 0) return MVO_OK;
     const int ngroups = guided_groups(nt_max), nbx = (n_map + 63) / 64;
     const size_t rows_all = (size_t)n_frames * n_map;
-    MVO_HIP(hipSetDevice(ctx->device));
     // pinned staging: the kernel writes its rows x 28 bytes of results straight into the first part; the second carries the
     // frame table, the masks, the gate's view of every keypoint and the descriptors up (one copy)
-    const size_t out_bytes = align64(rows_all * 28);
-    const size_t tab_b = align64((size_t)n_frames * sizeof(MapFuseFrame)), seen_b = align64((size_t)n_map * 8), tg_b = align64(total * 24);
-    const size_t in_bytes = tab_b + seen_b + tg_b + total * 32;
-    const size_t keys_b = align64(rows_all * ngroups * 8);
-    int r = ensure_bufs(ctx, in_bytes, keys_b + rows_all * ngroups * 4, (size_t)n_frames * nbx);
+    BlockCursor in;
+    const size_t i_tab = in.block((size_t)n_frames * sizeof(MapFuseFrame)), i_seen = in.block((size_t)n_map * 8);
+    const size_t i_tg = in.block(total * 24), i_desc = in.last(total * 32);
+    mvo_fuse_state* e = mvo_state(ctx->fuse);
+    StagedCall call{ctx};
+    int r = call.begin(e->d_in, in.bytes, (size_t)1 << 20, align64(rows_all * 28),
+                       [&] { return e->scratch.ensure(ctx, rows_all, ngroups, (size_t)n_frames * nbx); });
     if (r) return r;
-    mvo_fuse_state* e = ctx->fuse;
-    if ((r = mvo_ensure_pinned(ctx, out_bytes + in_bytes))) return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
-    uint8_t* h_in = ctx->h_pin + out_bytes;
-    MapFuseFrame* h_tab = reinterpret_cast<MapFuseFrame*>(h_in);
-    double* h_tg = reinterpret_cast<double*>(h_in + tab_b + seen_b);
-    uint8_t* h_desc = h_in + tab_b + seen_b + tg_b;
-    std::memcpy(h_in + tab_b, seen.data(), (size_t)n_map * 8);
-    size_t first = 0;
+    std::memcpy(call.h_in + i_seen, seen.data(), (size_t)n_map * 8);
+    const std::vector<FrameSlice> at =
+        guided_pack_frames(frames, n_frames, ngroups, reinterpret_cast<double*>(call.h_in + i_tg), call.h_in + i_desc,
+                           [max_px](const mvo_fuse_frame& F, int j) { return F.conn[j] == -2 ? -1.0 : guided_tol2(max_px, F.scale, j); });
+    MapFuseFrame* h_tab = reinterpret_cast<MapFuseFrame*>(call.h_in + i_tab);
     for (int f = 0; f < n_frames; ++f) {
-        const mvo_fuse_frame& F = frames[f];
         MapFuseFrame& row = h_tab[f];
         std::memcpy(row.T, &Tcw[12 * (size_t)f], sizeof row.T);
-        row.t = reinterpret_cast<const uint4*>(e->d_in + tab_b + seen_b + tg_b + first * 32);
-        row.tg = reinterpret_cast<const double*>(e->d_in + tab_b + seen_b + first * 24);
-        row.nt = F.n, row.slice = guided_slice(F.n, ngroups);
+        row.t = reinterpret_cast<const uint4*>(e->d_in + i_desc + at[f].first * 32);
+        row.tg = reinterpret_cast<const double*>(e->d_in + i_tg + at[f].first * 24);
+        row.nt = at[f].nt, row.slice = at[f].slice;
         row.pad[0] = row.pad[1] = 0;
-        for (int j = 0; j < F.n; ++j) {
-            double* g = h_tg + 3 * (first + j);
-            const double tl = max_px * (F.scale ? (double)F.scale[j] : 1.0);
-            g[0] = (double)F.xy[2 * j], g[1] = (double)F.xy[2 * j + 1];
-            g[2] = F.conn[j] == -2 ? -1.0 : tl * tl;
-        }
-        if (F.n) std::memcpy(h_desc + first * 32, F.desc, (size_t)F.n * 32);
-        first += (size_t)F.n;
     }
-    MVO_HIP(hipMemcpyAsync(e->d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = call.upload(e->d_in))) return r;
     MapFuseArgs a;
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
     a.cols = cols, a.rows = rows;
-    const GuidedPartials part = {reinterpret_cast<unsigned long long*>(e->d_part.p), reinterpret_cast<int32_t*>(e->d_part + keys_b),
-                                 e->d_arrive};
     ExtractGate gate(ctx);
-    if ((r = map_fuse_launch(ctx, map->d_pos, map->d_desc, n_map, a, reinterpret_cast<const MapFuseFrame*>(e->d_in.p), n_frames, ngroups,
-                             reinterpret_cast<const unsigned long long*>(e->d_in + tab_b), part, reinterpret_cast<int32_t*>(ctx->h_pin))))
+    if ((r = map_fuse_launch(ctx, map->d_pos, map->d_desc, n_map, a, reinterpret_cast<const MapFuseFrame*>(e->d_in + i_tab), n_frames,
+                             ngroups, reinterpret_cast<const unsigned long long*>(e->d_in + i_seen), e->scratch.partials(),
+                             reinterpret_cast<int32_t*>(call.h_out))) ||
+        (r = call.finish(gate)))
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     *launched = true;
     return MVO_OK;
 }

@@ -1,32 +1,12 @@
 // csrc/map_refine_host.cpp -- host side of the map-point position refinement (include/mvo_hip.h: mvo_map_refine_positions):
 // argument checks, the pose inverses, one upload, the launch, the results.  The kernel is in map_refine_kernels.hip, the
-// arithmetic in DESIGN.md section 18.  No other translation unit refers to this one: mvo_destroy reaches refine_release
-// through mvo_ctx::refine_release.
+// arithmetic in DESIGN.md section 18.  No other translation unit refers to this one.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "mvo_internal.h"
-
-namespace {
-
-void refine_release(mvo_ctx* ctx) {
-    delete ctx->refine;
-    ctx->refine = nullptr;
-}
-
-int ensure_bufs(mvo_ctx* ctx, size_t bytes) {
-    if (!ctx->refine) {
-        ctx->refine = new mvo_refine_state();
-        ctx->refine_release = refine_release;
-    }
-    return ctx->refine->d_in.ensure(ctx, bytes, (size_t)1 << 20);
-}
-
-inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
-
-}  // namespace
+#include "staged_call.h"
 
 extern "C" {
 
@@ -73,38 +53,34 @@ int mvo_map_refine_positions(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, in
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
     a.delta = P.huber_delta, a.rel_tol = P.rel_tolerance;
     a.max_trials = P.max_trials, a.min_obs = P.min_observations, a.n_frames = n_frames;
-    MVO_HIP(hipSetDevice(ctx->device));
     // pinned staging: the kernel writes chi2, positions, info and flags straight into the first part; the second carries the
     // inverted poses and the observation arrays up (one copy)
-    const size_t chi_b = align64((size_t)n * 16), pos_b = align64((size_t)n * 12), info_b = align64((size_t)n * 12);
-    const size_t out_bytes = chi_b + pos_b + info_b + align64((size_t)n_obs);
-    const size_t T_b = align64((size_t)n_frames * 96), uv_b = align64((size_t)n_obs * 8), fr_b = align64((size_t)n_obs * 4);
-    const size_t in_bytes = T_b + uv_b + fr_b + ((size_t)n + 1) * 4;
-    int r = ensure_bufs(ctx, in_bytes);
+    BlockCursor out, in;
+    const size_t o_chi2 = out.block((size_t)n * 16), o_pos = out.block((size_t)n * 12), o_info = out.block((size_t)n * 12);
+    const size_t o_flag = out.block((size_t)n_obs);
+    const size_t i_T = in.block((size_t)n_frames * 96), i_uv = in.block((size_t)n_obs * 8), i_frame = in.block((size_t)n_obs * 4);
+    const size_t i_start = in.last(((size_t)n + 1) * 4);
+    mvo_refine_state* e = mvo_state(ctx->refine);
+    StagedCall call{ctx};
+    int r = call.begin(e->d_in, in.bytes, (size_t)1 << 20, out.bytes);
     if (r) return r;
-    mvo_refine_state* e = ctx->refine;
-    if ((r = mvo_ensure_pinned(ctx, out_bytes + in_bytes))) return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
-    uint8_t* h_in = ctx->h_pin + out_bytes;
-    if (n_frames) std::memcpy(h_in, Tcw.data(), (size_t)n_frames * 96);
+    if (n_frames) std::memcpy(call.h_in + i_T, Tcw.data(), (size_t)n_frames * 96);
     if (n_obs) {
-        std::memcpy(h_in + T_b, obs_uv, (size_t)n_obs * 8);
-        std::memcpy(h_in + T_b + uv_b, obs_frame, (size_t)n_obs * 4);
+        std::memcpy(call.h_in + i_uv, obs_uv, (size_t)n_obs * 8);
+        std::memcpy(call.h_in + i_frame, obs_frame, (size_t)n_obs * 4);
     }
-    std::memcpy(h_in + T_b + uv_b + fr_b, obs_start, ((size_t)n + 1) * 4);
-    MVO_HIP(hipMemcpyAsync(e->d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    double* h_chi2 = reinterpret_cast<double*>(ctx->h_pin);
-    float* h_pos = reinterpret_cast<float*>(ctx->h_pin + chi_b);
-    int32_t* h_info = reinterpret_cast<int32_t*>(ctx->h_pin + chi_b + pos_b);
-    uint8_t* h_flag = ctx->h_pin + chi_b + pos_b + info_b;
+    std::memcpy(call.h_in + i_start, obs_start, ((size_t)n + 1) * 4);
+    if ((r = call.upload(e->d_in))) return r;
+    double* h_chi2 = reinterpret_cast<double*>(call.h_out + o_chi2);
+    float* h_pos = reinterpret_cast<float*>(call.h_out + o_pos);
+    int32_t* h_info = reinterpret_cast<int32_t*>(call.h_out + o_info);
+    uint8_t* h_flag = call.h_out + o_flag;
     ExtractGate gate(ctx);
-    if ((r = map_refine_launch(ctx, map->d_pos, n, a, reinterpret_cast<const double*>(e->d_in.p),
-                               reinterpret_cast<const float*>(e->d_in + T_b), reinterpret_cast<const int32_t*>(e->d_in + T_b + uv_b),
-                               reinterpret_cast<const int32_t*>(e->d_in + T_b + uv_b + fr_b), h_pos, h_chi2, h_info, h_flag)))
+    if ((r = map_refine_launch(ctx, map->d_pos, n, a, reinterpret_cast<const double*>(e->d_in + i_T),
+                               reinterpret_cast<const float*>(e->d_in + i_uv), reinterpret_cast<const int32_t*>(e->d_in + i_frame),
+                               reinterpret_cast<const int32_t*>(e->d_in + i_start), h_pos, h_chi2, h_info, h_flag)) ||
+        (r = call.finish(gate)))
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     std::memcpy(pos_out, h_pos, (size_t)n * 12);
     std::memcpy(chi2, h_chi2, (size_t)n * 16);
     std::memcpy(info, h_info, (size_t)n * 12);

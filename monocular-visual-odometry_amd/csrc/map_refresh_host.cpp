@@ -1,31 +1,11 @@
 // csrc/map_refresh_host.cpp -- host side of the map-point refresh (include/mvo_hip.h: mvo_map_refresh, mvo_debug_get_map):
 // argument checks, one upload of the observation arrays, the launch, the results.  The kernel is in map_refresh_kernels.hip,
-// the arithmetic in DESIGN.md section 17.  No other translation unit refers to this one: mvo_destroy reaches refresh_release
-// through mvo_ctx::refresh_release.
+// the arithmetic in DESIGN.md section 17.  No other translation unit refers to this one.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
-#include "mvo_internal.h"
-
-namespace {
-
-void refresh_release(mvo_ctx* ctx) {
-    delete ctx->refresh;
-    ctx->refresh = nullptr;
-}
-
-int ensure_bufs(mvo_ctx* ctx, size_t bytes) {
-    if (!ctx->refresh) {
-        ctx->refresh = new mvo_refresh_state();
-        ctx->refresh_release = refresh_release;
-    }
-    return ctx->refresh->d_in.ensure(ctx, bytes, (size_t)1 << 20);
-}
-
-inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
-
-}  // namespace
+#include "staged_call.h"
 
 extern "C" {
 
@@ -48,33 +28,29 @@ int mvo_map_refresh(mvo_ctx* ctx, mvo_map* map, const uint8_t* obs_desc, const d
         if (obs_start[i + 1] - obs_start[i] > MR_MAX_OBS) return invalid("more than 64 observations of a map point", MVO_ERR_CAPACITY);
     for (size_t k = 0; k < 3 * (size_t)n_obs; ++k)
         if (!std::isfinite(obs_cam[k])) return invalid("obs_cam is not finite");
-    MVO_HIP(hipSetDevice(ctx->device));
     // pinned staging: the kernel writes normals, descriptors and choices straight into the first part; the second carries
     // the observation arrays up (one copy)
-    const size_t norm_b = align64((size_t)n * 24), desc_b = align64((size_t)n * 32), out_bytes = norm_b + desc_b + align64((size_t)n * 4);
-    const size_t cam_b = align64((size_t)n_obs * 24), odesc_b = align64((size_t)n_obs * 32), in_bytes = cam_b + odesc_b + ((size_t)n + 1) * 4;
-    int r = ensure_bufs(ctx, in_bytes);
+    BlockCursor out, in;
+    const size_t o_norm = out.block((size_t)n * 24), o_desc = out.block((size_t)n * 32), o_choice = out.block((size_t)n * 4);
+    const size_t i_cam = in.block((size_t)n_obs * 24), i_desc = in.block((size_t)n_obs * 32), i_start = in.last(((size_t)n + 1) * 4);
+    mvo_refresh_state* e = mvo_state(ctx->refresh);
+    StagedCall call{ctx};
+    int r = call.begin(e->d_in, in.bytes, (size_t)1 << 20, out.bytes);
     if (r) return r;
-    mvo_refresh_state* e = ctx->refresh;
-    if ((r = mvo_ensure_pinned(ctx, out_bytes + in_bytes))) return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
-    uint8_t* h_in = ctx->h_pin + out_bytes;
     if (n_obs) {
-        std::memcpy(h_in, obs_cam, (size_t)n_obs * 24);
-        std::memcpy(h_in + cam_b, obs_desc, (size_t)n_obs * 32);
+        std::memcpy(call.h_in + i_cam, obs_cam, (size_t)n_obs * 24);
+        std::memcpy(call.h_in + i_desc, obs_desc, (size_t)n_obs * 32);
     }
-    std::memcpy(h_in + cam_b + odesc_b, obs_start, ((size_t)n + 1) * 4);
-    MVO_HIP(hipMemcpyAsync(e->d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    double* h_norm = reinterpret_cast<double*>(ctx->h_pin);
-    uint8_t* h_desc = ctx->h_pin + norm_b;
-    int32_t* h_choice = reinterpret_cast<int32_t*>(ctx->h_pin + norm_b + desc_b);
+    std::memcpy(call.h_in + i_start, obs_start, ((size_t)n + 1) * 4);
+    if ((r = call.upload(e->d_in))) return r;
+    double* h_norm = reinterpret_cast<double*>(call.h_out + o_norm);
+    uint8_t* h_desc = call.h_out + o_desc;
+    int32_t* h_choice = reinterpret_cast<int32_t*>(call.h_out + o_choice);
     ExtractGate gate(ctx);
-    if ((r = map_refresh_launch(ctx, map->d_pos, map->d_desc, n, e->d_in + cam_b, reinterpret_cast<const double*>(e->d_in.p),
-                                reinterpret_cast<const int32_t*>(e->d_in + cam_b + odesc_b), h_choice, h_desc, h_norm)))
+    if ((r = map_refresh_launch(ctx, map->d_pos, map->d_desc, n, e->d_in + i_desc, reinterpret_cast<const double*>(e->d_in + i_cam),
+                                reinterpret_cast<const int32_t*>(e->d_in + i_start), h_choice, h_desc, h_norm)) ||
+        (r = call.finish(gate)))
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     std::memcpy(choice, h_choice, (size_t)n * 4);
     std::memcpy(norm_out, h_norm, (size_t)n * 24);
     if (desc_out) std::memcpy(desc_out, h_desc, (size_t)n * 32);

@@ -181,15 +181,9 @@ void mvo_destroy(mvo_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     track_release(ctx);
-    if (ctx->undist_release) ctx->undist_release(ctx);
-    if (ctx->epi_release) ctx->epi_release(ctx);
-    if (ctx->proj_release) ctx->proj_release(ctx);
-    if (ctx->dist_release) ctx->dist_release(ctx);
-    if (ctx->refresh_release) ctx->refresh_release(ctx);
-    if (ctx->refine_release) ctx->refine_release(ctx);
-    if (ctx->fuse_release) ctx->fuse_release(ctx);
-    if (ctx->window_release) ctx->window_release(ctx);
-    if (ctx->pose_opt_release) ctx->pose_opt_release(ctx);
+    // (the per-feature states free their device buffers on the current device: here, not in ~mvo_ctx)
+    ctx->undist.reset(), ctx->epi.reset(), ctx->proj.reset(), ctx->dist.reset(), ctx->refresh.reset(), ctx->refine.reset();
+    ctx->fuse.reset(), ctx->window.reset(), ctx->pose_opt.reset();
     ba_pool_release(ctx);
     ctx->d_img.release(), ctx->d_mq.release(), ctx->d_mt.release(), ctx->d_mqxy.release(), ctx->d_mtxy.release(), ctx->d_mout.release();
     void* dev[] = {ctx->d_raw, ctx->d_blur, ctx->d_tabs, ctx->d_pyr_regs, ctx->d_kp, ctx->d_desc_buf, ctx->d_fh_slots, ctx->d_fh_line, ctx->d_fh_arrive};

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <atomic>
 #include <string>
 #include <vector>
@@ -55,8 +56,8 @@ inline void mvo_free_on_current_device(void* p) {
 }
 
 // One grow-on-demand device buffer: a pointer and its capacity in elements, owned once.  release() frees through
-// mvo_free_on_current_device, so an owner is destroyed only on the paths that have made ctx->device current: mvo_destroy
-// with its *_release hooks, and mvo_map_release.  Neither ensure preserves the contents.
+// mvo_free_on_current_device, so an owner is destroyed only on the paths that have made ctx->device current: mvo_destroy,
+// which resets the per-feature states of mvo_ctx, and mvo_map_release.  Neither ensure preserves the contents.
 template <class T>
 struct DevBuf {
     T* p = nullptr;
@@ -230,7 +231,7 @@ struct UndistortArgs {  // k_undistort_map: the model with 1 / fx, 1 / fy taken 
 struct UndistortRec {
     int32_t iu, iv;
 };
-struct mvo_undistort_state {  // owned by undistort_host.cpp, released through mvo_ctx::undist_release
+struct mvo_undistort_state {  // mvo_ctx::undist, used by undistort_host.cpp
     bool configured = false;
     mvo_undistort_params params{};  // as configured, coefficients beyond n_coeffs zeroed
     int w = 0, h = 0;
@@ -253,12 +254,22 @@ struct GuidedScratch {  // one per matcher; keys, counts and counters are one al
     void release();
     GuidedPartials partials() const { return {d_part, d_part_cnt, d_arrive}; }
 };
+struct FrameScratch {  // the same for the launches over every buffered frame: map fusion, window triangulation (method: guided_match_host.h)
+    DevBuf<uint8_t> d_part;    // partial key pairs, then the partial counts: one block per frame
+    DevBuf<int32_t> d_arrive;  // arrival counters, one per (frame, group of 64 queries): self re-arming, zeroed when allocated
+    size_t keys_b = 0;         // bytes of the key pairs of the last ensure
+    // rows_all = frames x queries, n_arrive = frames x groups of 64 queries
+    int ensure(mvo_ctx* ctx, size_t rows_all, int ngroups, size_t n_arrive);
+    GuidedPartials partials() const {
+        return {reinterpret_cast<unsigned long long*>(d_part.p), reinterpret_cast<int32_t*>(d_part.p + keys_b), d_arrive.p};
+    }
+};
 
 // pose-guided matching (epipolar_kernels.hip / epipolar_host.cpp)
 struct EpipolarArgs {  // k_knn2_epipolar: F row-major, x2^T F x1 = 0
     double f[9];
 };
-struct mvo_epipolar_state {  // owned by epipolar_host.cpp, released through mvo_ctx::epi_release
+struct mvo_epipolar_state {  // mvo_ctx::epi, used by epipolar_host.cpp
     DevBuf<uint8_t> d_q, d_t;  // staging of the host-pointer form
     DevBuf<float> d_qxy, d_txy;
     DevBuf<double> d_tol2;
@@ -266,7 +277,7 @@ struct mvo_epipolar_state {  // owned by epipolar_host.cpp, released through mvo
 };
 
 // tracking by projection (projection_kernels.hip / projection_host.cpp)
-struct mvo_projection_state {  // owned by projection_host.cpp, released through mvo_ctx::proj_release
+struct mvo_projection_state {  // mvo_ctx::proj, used by projection_host.cpp
     DevBuf<uint8_t> d_t;  // staging of the host-pointer form
     DevBuf<double> d_tg;  // nt x ((double)x, (double)y, r2): the gate's view of the frame keypoints
     GuidedScratch scratch;
@@ -291,7 +302,7 @@ struct DistLevel {  // step 1 / step 6 geometry of a level
     int minX, minY, width, height;
     int cell0, ncells;  // its cells in the table (cell row, cell column order)
 };
-struct mvo_orb_distribute_state {  // owned by orb_distribute_host.cpp, released through mvo_ctx::dist_release
+struct mvo_orb_distribute_state {  // mvo_ctx::dist, used by orb_distribute_host.cpp
     mvo_orb_distribute_params params{20, 7, 30, 19};
     // what the cell table below was made for
     bool made = false;
@@ -310,7 +321,7 @@ struct mvo_orb_distribute_state {  // owned by orb_distribute_host.cpp, released
 
 // map points refreshed from their observations (map_refresh_kernels.hip / map_refresh_host.cpp)
 #define MR_MAX_OBS 64  // observations per map point: one lane each
-struct mvo_refresh_state {  // owned by map_refresh_host.cpp, released through mvo_ctx::refresh_release
+struct mvo_refresh_state {  // mvo_ctx::refresh, used by map_refresh_host.cpp
     DevBuf<uint8_t> d_in;  // one upload per call: the camera centres, the descriptors, the n + 1 starts
 };
 
@@ -321,7 +332,7 @@ struct MapRefineArgs {
     double delta, rel_tol;  // huber_delta, rel_tolerance
     int32_t max_trials, min_obs, n_frames;
 };
-struct mvo_refine_state {  // owned by map_refine_host.cpp, released through mvo_ctx::refine_release
+struct mvo_refine_state {  // mvo_ctx::refine, used by map_refine_host.cpp
     DevBuf<uint8_t> d_in;  // one upload per call: the inverted poses, the pixels, the frame indices, the n + 1 starts
 };
 
@@ -337,10 +348,9 @@ struct MapFuseFrame {  // one row of k_map_fuse_search's per-frame table, read f
     int32_t nt, slice; // slice = guided_slice(nt, the launch's train groups)
     int32_t pad[2];
 };
-struct mvo_fuse_state {  // owned by map_fuse_host.cpp, released through mvo_ctx::fuse_release
-    DevBuf<uint8_t> d_in;      // one upload per call: the frame table, the seen masks, the parked keypoints, the descriptors
-    DevBuf<uint8_t> d_part;    // partial key pairs and counts of guided_knn2(), one block per frame
-    DevBuf<int32_t> d_arrive;  // arrival counters, one per (frame, group of 64 map points): self re-arming, zeroed when allocated
+struct mvo_fuse_state {  // mvo_ctx::fuse, used by map_fuse_host.cpp
+    DevBuf<uint8_t> d_in;  // one upload per call: the frame table, the seen masks, the parked keypoints, the descriptors
+    FrameScratch scratch;  // queries: the map points
 };
 
 // new map points triangulated against every buffered frame (window_triangulate_kernels.hip / window_triangulate_host.cpp;
@@ -368,10 +378,9 @@ struct WindowVerifyArgs {
     double fx, fy, cx, cy;
     double c2max, chi2, rf2;  // max_cos_parallax^2, max_reproj_chi2, ratio_factor^2
 };
-struct mvo_window_state {  // owned by window_triangulate_host.cpp, released through mvo_ctx::window_release
-    DevBuf<uint8_t> d_in;      // one upload per call: the frame table, curr (free flags, pixels, descriptors), the frames' keypoints
-    DevBuf<uint8_t> d_part;    // partial key pairs and counts of guided_knn2(), one block per frame
-    DevBuf<int32_t> d_arrive;  // arrival counters, one per (frame, group of 64 keypoints): self re-arming, zeroed when allocated
+struct mvo_window_state {  // mvo_ctx::window, used by window_triangulate_host.cpp
+    DevBuf<uint8_t> d_in;  // one upload per call: the frame table, curr (free flags, pixels, descriptors), the frames' keypoints
+    FrameScratch scratch;  // queries: the keypoints of curr
     DevBuf<WindowPairIn> d_pairs;  // the small upload in front of the verification
 };
 
@@ -391,7 +400,7 @@ struct PoseOptOut {  // what k_pose_optimize writes into the ctx's pinned stagin
     int32_t info[6];
     int32_t pad[2];
 };
-struct mvo_pose_opt_state {  // owned by pose_optimize_host.cpp, released through mvo_ctx::pose_opt_release
+struct mvo_pose_opt_state {  // mvo_ctx::pose_opt, used by pose_optimize_host.cpp
     DevBuf<uint8_t> d_in;    // one upload per call: pts3d, pts2d, inv_sigma2
     int n_rounds = 0;        // rows of the last call that launched (mvo_debug_get_pose_optimize)
     double rows[PO_MAX_ROUNDS * 6] = {0};
@@ -467,35 +476,19 @@ struct mvo_ctx {
     bool init_called = false;
     std::vector<float> init_p_curr;
     std::vector<double> init_cosang, init_pixdist;
-    // --- undistortion: allocated by the first mvo_undistort_configure.  mvo_destroy releases it through the pointer, so
-    // that mvo_api.cpp carries no reference into undistort_host.cpp (a build without that file still links)
-    mvo_undistort_state* undist = nullptr;
-    void (*undist_release)(mvo_ctx*) = nullptr;
-    // --- pose-guided matching: allocated by the first mvo_match_knn2_epipolar*, released like the undistortion
-    mvo_epipolar_state* epi = nullptr;
-    void (*epi_release)(mvo_ctx*) = nullptr;
-    // --- tracking by projection: allocated by the first mvo_map_match_knn2_projection*, released like the undistortion
-    mvo_projection_state* proj = nullptr;
-    void (*proj_release)(mvo_ctx*) = nullptr;
-    // --- cell-wise FAST + quadtree spread: allocated by the first mvo_orb_distribute_configure /
-    // mvo_calc_keypoints_distributed*, released like the undistortion
-    mvo_orb_distribute_state* dist = nullptr;
-    void (*dist_release)(mvo_ctx*) = nullptr;
-    // --- map points refreshed from their observations: allocated by the first mvo_map_refresh, released like the undistortion
-    mvo_refresh_state* refresh = nullptr;
-    void (*refresh_release)(mvo_ctx*) = nullptr;
-    // --- map point positions refined from their observations: allocated by the first mvo_map_refine_positions, released likewise
-    mvo_refine_state* refine = nullptr;
-    void (*refine_release)(mvo_ctx*) = nullptr;
-    // --- duplicate map points fused over the buffered frames: allocated by the first mvo_map_fuse*, released likewise
-    mvo_fuse_state* fuse = nullptr;
-    void (*fuse_release)(mvo_ctx*) = nullptr;
-    // --- new map points triangulated against the buffered frames: allocated by the first mvo_window_triangulate*, released likewise
-    mvo_window_state* window = nullptr;
-    void (*window_release)(mvo_ctx*) = nullptr;
-    // --- the pose from a robust motion-only optimisation: allocated by the first mvo_optimize_pose, released likewise
-    mvo_pose_opt_state* pose_opt = nullptr;
-    void (*pose_opt_release)(mvo_ctx*) = nullptr;
+    // --- per-feature state, each made by the first call of its feature (mvo_state) and reset by mvo_destroy: undistortion,
+    // pose-guided matching, tracking by projection, cell-wise FAST + quadtree spread, map points refreshed from / refined over
+    // their observations, duplicate map points fused, new map points triangulated against the buffered frames, the pose from
+    // a robust motion-only optimisation
+    std::unique_ptr<mvo_undistort_state> undist;
+    std::unique_ptr<mvo_epipolar_state> epi;
+    std::unique_ptr<mvo_projection_state> proj;
+    std::unique_ptr<mvo_orb_distribute_state> dist;
+    std::unique_ptr<mvo_refresh_state> refresh;
+    std::unique_ptr<mvo_refine_state> refine;
+    std::unique_ptr<mvo_fuse_state> fuse;
+    std::unique_ptr<mvo_window_state> window;
+    std::unique_ptr<mvo_pose_opt_state> pose_opt;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -508,7 +501,12 @@ struct mvo_ctx {
     std::vector<std::pair<std::string, std::pair<hipEvent_t, hipEvent_t>>> prof_pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pool;
 };
-
+// a per-feature state of mvo_ctx, made on first use
+template <class State>
+State* mvo_state(std::unique_ptr<State>& p) {
+    if (!p) p.reset(new State());
+    return p.get();
+}
 
 // profiling brackets
 void mvo_prof_begin(mvo_ctx* c, const char* name);

@@ -2,8 +2,7 @@
 // mvo_calc_keypoints_distributed, its _dev form, mvo_debug_get_distribute_candidates): the cell table of an image geometry,
 // the orchestration of k_fast_cells and k_ic_angle (orb_distribute_kernels.hip) and the quadtree spread.  The arithmetic is
 // declared in DESIGN.md section 16.  The quadtree stays on the host for the reason retainBest does (orb_host.cpp): it is
-// order-sensitive and handles <= 10^4 items.  No other translation unit refers to this one: mvo_destroy reaches
-// distribute_release through mvo_ctx::dist_release.
+// order-sensitive and handles <= 10^4 items.  No other translation unit refers to this one.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -20,19 +19,6 @@ namespace {
 
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-void distribute_release(mvo_ctx* ctx) {
-    delete ctx->dist;
-    ctx->dist = nullptr;
-}
-
-mvo_orb_distribute_state* state(mvo_ctx* ctx) {
-    if (!ctx->dist) {
-        ctx->dist = new mvo_orb_distribute_state();
-        ctx->dist_release = distribute_release;
-    }
-    return ctx->dist;
-}
 
 // (u, v) of the pixels of cv::ORB's intensity-centroid disc (halfPatchSize 15, the umax table), row-major
 int ic_disc(signed char* disc) {
@@ -60,7 +46,7 @@ int ic_disc(signed char* disc) {
 // Step 1 for every level of the pyramid of ctx (orb_setup_geometry has run): the cell table, the record slots, the levels'
 // quadtree extents.  Made once per (image size, ORB parameters, detector parameters).
 int setup_cells(mvo_ctx* ctx, int w, int h) {
-    mvo_orb_distribute_state* s = state(ctx);
+    mvo_orb_distribute_state* s = mvo_state(ctx->dist);
     if (s->made && s->made_w == w && s->made_h == h && !std::memcmp(&s->made_orb, &ctx->orb, sizeof ctx->orb) &&
         !std::memcmp(&s->made_params, &s->params, sizeof s->params))
         return MVO_OK;
@@ -232,7 +218,7 @@ int detect_device(mvo_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, 
     int r = orb_setup_geometry(ctx, w, h);
     if (r) return r;
     if ((r = setup_cells(ctx, w, h))) return r;
-    mvo_orb_distribute_state* s = ctx->dist;
+    mvo_orb_distribute_state* s = ctx->dist.get();
     const PyrInfo& P = ctx->pyr;
     const int n_cells = (int)s->cells.size();
     ctx->pyr_valid = ctx->blur_valid = false;
@@ -357,7 +343,7 @@ int mvo_orb_distribute_configure(mvo_ctx* ctx, const mvo_orb_distribute_params* 
     if (p->ini_threshold < 1 || p->ini_threshold > 255 || p->min_threshold < 1 || p->min_threshold > p->ini_threshold ||
         p->cell_size < 8 || p->cell_size > DC_MAX_CELL_SIZE || p->edge_threshold < 19 || p->edge_threshold > 31)
         return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_orb_distribute_configure: parameter out of range", hipSuccess);
-    state(ctx)->params = *p;
+    mvo_state(ctx->dist)->params = *p;
     return MVO_OK;
 }
 

@@ -1,30 +1,11 @@
 // csrc/pose_optimize_host.cpp -- host side of the robust motion-only pose optimisation (include/mvo_hip.h: mvo_optimize_pose,
 // mvo_debug_get_pose_optimize): argument checks, the inverse of the initial pose, one upload, the launch, the results and the
 // inverse of the final state.  The kernel is in pose_optimize_kernels.hip, the arithmetic in DESIGN.md section 21.  No other
-// translation unit refers to this one: mvo_destroy reaches pose_opt_release through mvo_ctx::pose_opt_release.
+// translation unit refers to this one.
 #include <cmath>
 #include <cstring>
 
-#include "mvo_internal.h"
-
-namespace {
-
-void pose_opt_release(mvo_ctx* ctx) {
-    delete ctx->pose_opt;
-    ctx->pose_opt = nullptr;
-}
-
-int ensure_bufs(mvo_ctx* ctx, size_t bytes) {
-    if (!ctx->pose_opt) {
-        ctx->pose_opt = new mvo_pose_opt_state();
-        ctx->pose_opt_release = pose_opt_release;
-    }
-    return ctx->pose_opt->d_in.ensure(ctx, bytes, (size_t)1 << 16);
-}
-
-inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
-
-}  // namespace
+#include "staged_call.h"
 
 extern "C" {
 
@@ -73,31 +54,26 @@ int mvo_optimize_pose(mvo_ctx* ctx, const float* pts3d, const float* pts2d, cons
     a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
     a.delta = P.huber_delta, a.chi2_thr = P.chi2_threshold, a.rel_tol = P.rel_tolerance;
     a.rounds = P.rounds, a.iterations = P.iterations, a.min_inliers = P.min_inliers, a.has_sigma = inv_sigma2 ? 1 : 0;
-    MVO_HIP(hipSetDevice(ctx->device));
     // pinned staging: the kernel writes the pose, chi2, the rows, info and the flags straight into the first part; the second
     // carries the observations up (one copy)
-    const size_t out_bytes = align64(sizeof(PoseOptOut)) + align64((size_t)n);
-    const size_t p3_b = align64((size_t)n * 12), p2_b = align64((size_t)n * 8);
-    const size_t in_bytes = p3_b + p2_b + (inv_sigma2 ? (size_t)n * 4 : 0);
-    int r = ensure_bufs(ctx, in_bytes);
+    BlockCursor out, in;
+    const size_t o_out = out.block(sizeof(PoseOptOut)), o_flag = out.block((size_t)n);
+    const size_t i_p3 = in.block((size_t)n * 12), i_p2 = in.block((size_t)n * 8), i_sigma = in.last(inv_sigma2 ? (size_t)n * 4 : 0);
+    mvo_pose_opt_state* e = mvo_state(ctx->pose_opt);
+    StagedCall call{ctx};
+    int r = call.begin(e->d_in, in.bytes, (size_t)1 << 16, out.bytes);
     if (r) return r;
-    mvo_pose_opt_state* e = ctx->pose_opt;
-    if ((r = mvo_ensure_pinned(ctx, out_bytes + in_bytes))) return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
-    uint8_t* h_in = ctx->h_pin + out_bytes;
-    std::memcpy(h_in, pts3d, (size_t)n * 12);
-    std::memcpy(h_in + p3_b, pts2d, (size_t)n * 8);
-    if (inv_sigma2) std::memcpy(h_in + p3_b + p2_b, inv_sigma2, (size_t)n * 4);
-    MVO_HIP(hipMemcpyAsync(e->d_in, h_in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    PoseOptOut* h_out = reinterpret_cast<PoseOptOut*>(ctx->h_pin);
-    uint8_t* h_flag = ctx->h_pin + align64(sizeof(PoseOptOut));
+    std::memcpy(call.h_in + i_p3, pts3d, (size_t)n * 12);
+    std::memcpy(call.h_in + i_p2, pts2d, (size_t)n * 8);
+    if (inv_sigma2) std::memcpy(call.h_in + i_sigma, inv_sigma2, (size_t)n * 4);
+    if ((r = call.upload(e->d_in))) return r;
+    PoseOptOut* h_out = reinterpret_cast<PoseOptOut*>(call.h_out + o_out);
+    uint8_t* h_flag = call.h_out + o_flag;
     ExtractGate gate(ctx);
-    if ((r = pose_optimize_launch(ctx, reinterpret_cast<const float*>(e->d_in.p), reinterpret_cast<const float*>(e->d_in + p3_b),
-                                  inv_sigma2 ? reinterpret_cast<const float*>(e->d_in + p3_b + p2_b) : nullptr, n, a, h_out, h_flag)))
+    if ((r = pose_optimize_launch(ctx, reinterpret_cast<const float*>(e->d_in + i_p3), reinterpret_cast<const float*>(e->d_in + i_p2),
+                                  inv_sigma2 ? reinterpret_cast<const float*>(e->d_in + i_sigma) : nullptr, n, a, h_out, h_flag)) ||
+        (r = call.finish(gate)))
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     const int status = h_out->info[0];
     double Tcw[16], Twc[16];
     std::memcpy(Tcw, h_out->Tcw, sizeof h_out->Tcw);
@@ -121,7 +97,7 @@ int mvo_debug_get_pose_optimize(mvo_ctx* ctx, double* rows, int cap, int* n_roun
     if (!ctx) return MVO_ERR_INVALID;
     if (!ctx->pose_opt) return mvo_set_err(ctx, MVO_ERR_STATE, "no mvo_optimize_pose launch on this ctx yet", hipSuccess);
     if (!n_rounds || cap < 0 || (cap && !rows)) return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_debug_get_pose_optimize: bad arguments", hipSuccess);
-    const mvo_pose_opt_state* e = ctx->pose_opt;
+    const mvo_pose_opt_state* e = ctx->pose_opt.get();
     *n_rounds = e->n_rounds;
     if (cap < e->n_rounds) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "mvo_debug_get_pose_optimize: buffer too small", hipSuccess);
     if (e->n_rounds) std::memcpy(rows, e->rows, (size_t)e->n_rounds * 6 * sizeof(double));

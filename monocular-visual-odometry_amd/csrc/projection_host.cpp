@@ -1,8 +1,7 @@
 // csrc/projection_host.cpp -- host side of tracking by projection (include/mvo_hip.h: mvo_map_match_knn2_projection,
 // mvo_map_match_knn2_projection_dev, mvo_map_match_features_projection, mvo_map_size, mvo_predict_pose): argument checks, the per-keypoint
 // radius, staging, the filter and the one-query-per-train rule.  The kernel is in projection_kernels.hip, the arithmetic in
-// DESIGN.md section 15.  No other translation unit refers to this one: mvo_destroy reaches projection_release through
-// mvo_ctx::proj_release.
+// DESIGN.md section 15.  No other translation unit refers to this one.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -14,25 +13,14 @@
 
 namespace {
 
-void projection_release(mvo_ctx* ctx) {
-    delete ctx->proj;
-    ctx->proj = nullptr;
-}
-
 int ensure_bufs(mvo_ctx* ctx, int n_map, int nt) {
-    if (!ctx->proj) {
-        ctx->proj = new mvo_projection_state();
-        ctx->proj_release = projection_release;
-    }
-    mvo_projection_state* e = ctx->proj;
+    mvo_projection_state* e = mvo_state(ctx->proj);
     int r;
     if ((r = e->scratch.ensure(ctx, n_map)) || (r = e->d_t.ensure(ctx, (size_t)nt * 32, 4096 * 32)) ||
         (r = e->d_tg.ensure(ctx, (size_t)nt * 3, 4096 * 3)))
         return r;
     return MVO_OK;
 }
-
-inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
 
 // Every form: the checks, the upload, the launch, the results.  t is a host pointer (t_on_device false) or a device pointer.
 int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy, int cols, int rows,
@@ -63,7 +51,7 @@ int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, d
     MVO_HIP(hipSetDevice(ctx->device));
     int r = ensure_bufs(ctx, n_map, nt);
     if (r) return r;
-    mvo_projection_state* e = ctx->proj;
+    mvo_projection_state* e = ctx->proj.get();
     // pinned staging: the kernel writes its n_map x 28 bytes of results straight into the first part; the second carries the
     // gate's view of the frame keypoints up (one copy)
     const size_t out_bytes = align64((size_t)n_map * 28);
@@ -85,11 +73,9 @@ int run(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, d
         }
     }
     ExtractGate gate(ctx);
-    if ((r = projection_launch(ctx, map->d_pos, map->d_desc, n_map, a, d_t, e->d_tg, nt, e->scratch.partials(), h_out)))
+    if ((r = projection_launch(ctx, map->d_pos, map->d_desc, n_map, a, d_t, e->d_tg, nt, e->scratch.partials(), h_out)) ||
+        (r = StagedCall{ctx}.finish(gate)))
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     std::memcpy(idx, ctx->h_pin, (size_t)n_map * 8);
     std::memcpy(dist, ctx->h_pin + (size_t)n_map * 8, (size_t)n_map * 8);
     if (px) std::memcpy(px, ctx->h_pin + (size_t)n_map * 16, (size_t)n_map * 8);

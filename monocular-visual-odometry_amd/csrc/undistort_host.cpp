@@ -1,7 +1,7 @@
 // csrc/undistort_host.cpp -- host side of the undistortion (include/mvo_hip.h: mvo_undistort_configure, mvo_undistort,
 // mvo_undistort_dev, mvo_debug_get_undistort_map): argument checks, the cached map of a configuration, the staging of
 // the host-pointer form.  The kernels are in undistort_kernels.hip, the arithmetic in DESIGN.md section 13.  No other
-// translation unit refers to this one: mvo_destroy reaches undistort_release through mvo_ctx::undist_release.
+// translation unit refers to this one.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -12,11 +12,6 @@ namespace {
 
 const int kMaxWidth = 8192;            // as the extraction (FT_ROW_TILES)
 const long long kMaxPixels = 1 << 30;  // pixel indices are 32-bit in the kernels, the debug getter counts in int
-
-void undistort_release(mvo_ctx* ctx) {
-    delete ctx->undist;
-    ctx->undist = nullptr;
-}
 
 // the parameters as they are compared and used: coefficients beyond n_coeffs are 0.  false: not a supported model
 bool normalise(const mvo_undistort_params& in, mvo_undistort_params* out) {
@@ -37,7 +32,7 @@ int check_call(mvo_ctx* ctx, const void* img, int w, int h, int stride, int ch, 
     if (!ctx) return MVO_ERR_INVALID;
     if (!img || !out || w < 1 || h < 1 || w > kMaxWidth || (ch != 1 && ch != 3 && ch != 4) || stride < w * ch || out_stride < w * ch)
         return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_undistort: bad image arguments", hipSuccess);
-    const mvo_undistort_state* u = ctx->undist;
+    const mvo_undistort_state* u = ctx->undist.get();
     if (!u || !u->configured)
         return mvo_set_err(ctx, MVO_ERR_STATE, "mvo_undistort before mvo_undistort_configure", hipSuccess);
     if (u->w != w || u->h != h)
@@ -60,11 +55,7 @@ int mvo_undistort_configure(mvo_ctx* ctx, const mvo_undistort_params* params, in
     if (width < 1 || height < 1 || width > kMaxWidth || (long long)width * height > kMaxPixels)
         return mvo_set_err(ctx, MVO_ERR_INVALID, "mvo_undistort_configure: image size out of range", hipSuccess);
     MVO_HIP(hipSetDevice(ctx->device));
-    if (!ctx->undist) {
-        ctx->undist = new mvo_undistort_state();
-        ctx->undist_release = undistort_release;
-    }
-    mvo_undistort_state* u = ctx->undist;
+    mvo_undistort_state* u = mvo_state(ctx->undist);
     if (u->configured && u->w == width && u->h == height && !std::memcmp(&u->params, &p, sizeof p)) return MVO_OK;
     u->configured = false;
     int r = u->d_map.ensure_exact(ctx, (size_t)width * height, 64);
@@ -95,7 +86,7 @@ int mvo_undistort(mvo_ctx* ctx, const uint8_t* image, int w, int h, int stride, 
     int r = check_call(ctx, image, w, h, stride, ch, out, out_stride);
     if (r) return r;
     MVO_HIP(hipSetDevice(ctx->device));
-    mvo_undistort_state* u = ctx->undist;
+    mvo_undistort_state* u = ctx->undist.get();
     const size_t in_bytes = extent(w, h, stride, ch), row = (size_t)w * ch;
     if ((r = u->d_src.ensure_exact(ctx, in_bytes, 64))) return r;
     if ((r = u->d_dst.ensure_exact(ctx, row * h, 64))) return r;
@@ -117,7 +108,7 @@ int mvo_undistort(mvo_ctx* ctx, const uint8_t* image, int w, int h, int stride, 
 
 int mvo_debug_get_undistort_map(mvo_ctx* ctx, int32_t* ix, int32_t* iy, uint8_t* ax, uint8_t* ay, int cap) {
     if (!ctx) return MVO_ERR_INVALID;
-    const mvo_undistort_state* u = ctx->undist;
+    const mvo_undistort_state* u = ctx->undist.get();
     if (!u || !u->configured) return mvo_set_err(ctx, MVO_ERR_STATE, "no undistortion map: call mvo_undistort_configure first", hipSuccess);
     const size_t n = (size_t)u->w * u->h;
     if (cap < 0 || (size_t)cap < n) return mvo_set_err(ctx, MVO_ERR_CAPACITY, "undistortion map buffer too small", hipSuccess);

@@ -2,7 +2,7 @@
 // (include/mvo_hip.h: mvo_window_triangulate_search, mvo_window_triangulate): argument checks, the relative poses and the
 // fundamental matrices, one upload, the search launch, the filter (guided_match_host.h), one small upload, the verification
 // launch and the choice.  The kernels are in window_triangulate_kernels.hip, the rule in DESIGN.md section 20.  No other
-// translation unit refers to this one: mvo_destroy reaches window_release through mvo_ctx::window_release.
+// translation unit refers to this one.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -10,47 +10,14 @@
 #include <string>
 #include <vector>
 
-#include "guided_knn2.h"
 #include "guided_match_host.h"
 
 namespace {
-
-void window_release(mvo_ctx* ctx) {
-    delete ctx->window;
-    ctx->window = nullptr;
-}
-
-inline size_t align64(size_t b) { return (b + 63) / 64 * 64; }
-
-int ensure_bufs(mvo_ctx* ctx, size_t in_bytes, size_t part_bytes, size_t n_arrive) {
-    if (!ctx->window) {
-        ctx->window = new mvo_window_state();
-        ctx->window_release = window_release;
-    }
-    mvo_window_state* e = ctx->window;
-    int r;
-    if ((r = e->d_in.ensure(ctx, in_bytes, (size_t)1 << 20)) || (r = e->d_part.ensure(ctx, part_bytes, (size_t)1 << 18))) return r;
-    const size_t had = e->d_arrive.cap;
-    if ((r = e->d_arrive.ensure(ctx, n_arrive, 4096))) return r;
-    if (e->d_arrive.cap != had)  // the counters re-arm themselves: zeroed once per allocation
-        MVO_HIP(hipMemsetAsync(e->d_arrive, 0, e->d_arrive.cap * sizeof(int32_t), ctx->stream));
-    return MVO_OK;
-}
-
-struct Layout {  // the one upload, by byte offsets into d_in
-    size_t tab_b = 0, free_b = 0, cxy_b = 0, cdesc_b = 0, tg_b = 0, in_bytes = 0;
-    size_t off_free() const { return tab_b; }
-    size_t off_cxy() const { return tab_b + free_b; }
-    size_t off_cdesc() const { return tab_b + free_b + cxy_b; }
-    size_t off_tg() const { return tab_b + free_b + cxy_b + cdesc_b; }
-    size_t off_desc() const { return off_tg() + tg_b; }
-};
 
 struct Search {
     std::vector<WindowFrame> rows;  // device pointers not yet set
     int n_free = 0, n_active = 0;
     bool launched = false;
-    Layout lay;
 };
 
 // The checks, the upload, the launch, the wait.  On success, when s.launched, the raw results lie in ctx->h_pin: idx, dist,
@@ -66,15 +33,8 @@ int search(mvo_ctx* ctx, const mvo_fuse_frame* curr, const mvo_fuse_frame* frame
         return fail("fx or fy 0, or intrinsics not finite");
     if (!(max_line_px >= 0)) return fail("max_line_px negative or NaN");
     if (!(min_baseline >= 0)) return fail("min_baseline negative or NaN");
-    auto check_frame = [&](const mvo_fuse_frame& F) -> int {
-        if (F.n < 0 || (F.n && (!F.desc || !F.xy || !F.conn))) return fail("bad arguments");
-        if (F.n > 65535) return fail("more than 65535 keypoints in a frame", MVO_ERR_CAPACITY);
-        for (int k = 0; k < 16; ++k)
-            if (!std::isfinite(F.T_w_c[k])) return fail("T_w_c is not finite");
-        for (int j = 0; F.scale && j < F.n; ++j)
-            if (!std::isfinite(F.scale[j]) || F.scale[j] < 0) return fail("scale entry negative or not finite");
-        return MVO_OK;
-    };
+    // (the inverse is not asked for: a singular pose is reported behind the scales, by the calls below)
+    auto check_frame = [&](const mvo_fuse_frame& F) { return guided_check_frame(F, nullptr, fail, [](int) { return (int)MVO_OK; }); };
     if (int r = check_frame(*curr)) return r;
     double Tci[16];
     if (mvo_invert_pose(curr->T_w_c, Tci) != MVO_OK) return fail("T_w_c is singular");
@@ -109,53 +69,37 @@ int search(mvo_ctx* ctx, const mvo_fuse_frame* curr, const mvo_fuse_frame* frame
     if (n_frames == 0 || s.n_free == 0) return MVO_OK;
     const int ngroups = guided_groups(nt_max), nbx = (nq + 63) / 64;
     const size_t rows_all = (size_t)n_frames * nq;
-    MVO_HIP(hipSetDevice(ctx->device));
     // pinned staging: the kernel writes its rows x 20 bytes of results straight into the first part; the second carries the
-    // frame table, curr and the gate's view and the descriptors of every frame up (one copy)
-    const size_t out_bytes = align64(rows_all * 20);
-    Layout& L = s.lay;
-    L.tab_b = align64((size_t)n_frames * sizeof(WindowFrame)), L.free_b = align64((size_t)nq), L.cxy_b = align64((size_t)nq * 8);
-    L.cdesc_b = align64((size_t)nq * 32), L.tg_b = align64(total * 24);
-    L.in_bytes = L.off_desc() + total * 32;
-    const size_t keys_b = align64(rows_all * ngroups * 8);
-    int r = ensure_bufs(ctx, L.in_bytes, keys_b + rows_all * ngroups * 4, (size_t)n_frames * nbx);
+    // frame table (first in d_in: the verification reads it there), curr and the gate's view and the descriptors of every frame
+    // up (one copy)
+    BlockCursor in;
+    const size_t i_tab = in.block((size_t)n_frames * sizeof(WindowFrame)), i_free = in.block((size_t)nq), i_cxy = in.block((size_t)nq * 8);
+    const size_t i_cdesc = in.block((size_t)nq * 32), i_tg = in.block(total * 24), i_desc = in.last(total * 32);
+    mvo_window_state* e = mvo_state(ctx->window);
+    StagedCall call{ctx};
+    int r = call.begin(e->d_in, in.bytes, (size_t)1 << 20, align64(rows_all * 20),
+                       [&] { return e->scratch.ensure(ctx, rows_all, ngroups, (size_t)n_frames * nbx); });
     if (r) return r;
-    mvo_window_state* e = ctx->window;
-    if ((r = mvo_ensure_pinned(ctx, out_bytes + L.in_bytes))) return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));  // (nothing of an earlier call may still be reading the staging buffer)
-    uint8_t* h_in = ctx->h_pin + out_bytes;
-    for (int i = 0; i < nq; ++i) h_in[L.off_free() + i] = curr->conn[i] == -1 ? 1 : 0;
-    std::memcpy(h_in + L.off_cxy(), curr->xy, (size_t)nq * 8);
-    std::memcpy(h_in + L.off_cdesc(), curr->desc, (size_t)nq * 32);
-    double* h_tg = reinterpret_cast<double*>(h_in + L.off_tg());
-    uint8_t* h_desc = h_in + L.off_desc();
-    size_t first = 0;
+    for (int i = 0; i < nq; ++i) call.h_in[i_free + i] = curr->conn[i] == -1 ? 1 : 0;
+    std::memcpy(call.h_in + i_cxy, curr->xy, (size_t)nq * 8);
+    std::memcpy(call.h_in + i_cdesc, curr->desc, (size_t)nq * 32);
+    const std::vector<FrameSlice> at =
+        guided_pack_frames(frames, n_frames, ngroups, reinterpret_cast<double*>(call.h_in + i_tg), call.h_in + i_desc,
+                           [max_line_px](const mvo_fuse_frame& F, int j) { return F.conn[j] == -1 ? guided_tol2(max_line_px, F.scale, j) : -1.0; });
     for (int f = 0; f < n_frames; ++f) {
-        const mvo_fuse_frame& F = frames[f];
         WindowFrame& row = s.rows[f];
-        row.d = reinterpret_cast<const uint4*>(e->d_in + L.off_desc() + first * 32);
-        row.tg = reinterpret_cast<const double*>(e->d_in + L.off_tg() + first * 24);
-        row.slice = guided_slice(F.n, ngroups);
-        for (int j = 0; j < F.n; ++j) {
-            double* g = h_tg + 3 * (first + j);
-            g[0] = (double)F.xy[2 * j], g[1] = (double)F.xy[2 * j + 1];
-            g[2] = F.conn[j] == -1 ? guided_tol2(max_line_px, F.scale, j) : -1.0;
-        }
-        if (F.n) std::memcpy(h_desc + first * 32, F.desc, (size_t)F.n * 32);
-        first += (size_t)F.n;
+        row.d = reinterpret_cast<const uint4*>(e->d_in + i_desc + at[f].first * 32);
+        row.tg = reinterpret_cast<const double*>(e->d_in + i_tg + at[f].first * 24);
+        row.slice = at[f].slice;
     }
-    std::memcpy(h_in, s.rows.data(), (size_t)n_frames * sizeof(WindowFrame));
-    MVO_HIP(hipMemcpyAsync(e->d_in, h_in, L.in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const GuidedPartials part = {reinterpret_cast<unsigned long long*>(e->d_part.p), reinterpret_cast<int32_t*>(e->d_part + keys_b),
-                                 e->d_arrive};
+    std::memcpy(call.h_in + i_tab, s.rows.data(), (size_t)n_frames * sizeof(WindowFrame));
+    if ((r = call.upload(e->d_in))) return r;
     ExtractGate gate(ctx);
-    if ((r = window_launch_search(ctx, e->d_in + L.off_cdesc(), reinterpret_cast<const float*>(e->d_in + L.off_cxy()), e->d_in + L.off_free(),
-                                  nq, reinterpret_cast<const WindowFrame*>(e->d_in.p), n_frames, ngroups, part,
-                                  reinterpret_cast<int32_t*>(ctx->h_pin))))
+    if ((r = window_launch_search(ctx, e->d_in + i_cdesc, reinterpret_cast<const float*>(e->d_in + i_cxy), e->d_in + i_free, nq,
+                                  reinterpret_cast<const WindowFrame*>(e->d_in + i_tab), n_frames, ngroups, e->scratch.partials(),
+                                  reinterpret_cast<int32_t*>(call.h_out))) ||
+        (r = call.finish(gate)))
         return r;
-    MVO_HIP(hipStreamSynchronize(ctx->stream));
-    gate.release();
-    if (ctx->prof) mvo_prof_collect(ctx);
     s.launched = true;
     return MVO_OK;
 }
@@ -229,30 +173,31 @@ int mvo_window_triangulate(mvo_ctx* ctx, const mvo_fuse_frame* curr, const mvo_f
     cnt[3] = np;
     if (np) {
         // (the results of the search have been read: the staging buffer is free again; the frame table stays on the device)
-        mvo_window_state* e = ctx->window;
+        // The device is current and the stream idle behind the search, and the pairs have a buffer of their own type: stage()
+        // in place of begin()
+        mvo_window_state* e = ctx->window.get();
+        StagedCall call{ctx};
         int r;
-        if ((r = e->d_pairs.ensure(ctx, (size_t)np, 4096))) return r;
-        const size_t out_bytes = align64((size_t)np * sizeof(WindowPairOut));
-        if ((r = mvo_ensure_pinned(ctx, out_bytes + (size_t)np * sizeof(WindowPairIn)))) return r;
-        WindowPairIn* h_pairs = reinterpret_cast<WindowPairIn*>(ctx->h_pin + out_bytes);
+        if ((r = e->d_pairs.ensure(ctx, (size_t)np, 4096)) ||
+            (r = call.stage(align64((size_t)np * sizeof(WindowPairOut)), (size_t)np * sizeof(WindowPairIn))))
+            return r;
+        WindowPairIn* h_pairs = reinterpret_cast<WindowPairIn*>(call.h_in);
         for (int a = 0; a < np; ++a) {
             const mvo_fuse_frame& F = frames[pr[a].frame];
             const int i = pr[a].keypoint, j = pr[a].train;
             h_pairs[a] = {pr[a].frame, 0, F.xy[2 * j], F.xy[2 * j + 1], curr->xy[2 * i], curr->xy[2 * i + 1], F.scale ? F.scale[j] : 1.0f,
                           curr->scale ? curr->scale[i] : 1.0f};
         }
-        MVO_HIP(hipMemcpyAsync(e->d_pairs, h_pairs, (size_t)np * sizeof(WindowPairIn), hipMemcpyHostToDevice, ctx->stream));
+        if ((r = call.upload(e->d_pairs))) return r;
         WindowVerifyArgs a;
         a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy;
         a.c2max = P.max_cos_parallax * P.max_cos_parallax, a.chi2 = P.max_reproj_chi2, a.rf2 = P.ratio_factor * P.ratio_factor;
         ExtractGate gate(ctx);
         if ((r = window_launch_verify(ctx, e->d_pairs, np, reinterpret_cast<const WindowFrame*>(e->d_in.p), a,
-                                      reinterpret_cast<WindowPairOut*>(ctx->h_pin))))
+                                      reinterpret_cast<WindowPairOut*>(call.h_out))) ||
+            (r = call.finish(gate)))
             return r;
-        MVO_HIP(hipStreamSynchronize(ctx->stream));
-        gate.release();
-        if (ctx->prof) mvo_prof_collect(ctx);
-        const WindowPairOut* o = reinterpret_cast<const WindowPairOut*>(ctx->h_pin);
+        const WindowPairOut* o = reinterpret_cast<const WindowPairOut*>(call.h_out);
         for (int k = 0; k < np; ++k) {
             std::memcpy(pr[k].p_curr, o[k].p_curr, sizeof pr[k].p_curr);
             std::memcpy(pr[k].p_frame, o[k].p_frame, sizeof pr[k].p_frame);

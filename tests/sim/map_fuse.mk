@@ -8,6 +8,6 @@ include map_refine.mk
 MAP_FUSE_OBJ := $(MAP_REFINE_OBJ) _build/full/map_fuse_host.cpp.o _build/full/map_fuse_kernels.hip.o
 _build/full/map_fuse_kernels.hip.o: FLAGS += -include hip_emu_grid3d/launch_3d.h
 _build/full/map_fuse_kernels.hip.o: hip_emu_grid3d/launch_3d.h $(CSRC)/guided_knn2.h
-_build/full/map_fuse_host.cpp.o: $(CSRC)/guided_knn2.h
+_build/full/map_fuse_host.cpp.o: $(CSRC)/guided_knn2.h $(CSRC)/guided_match_host.h
 _build/libmvo_sim_map_fuse.so: $(MAP_FUSE_OBJ)
 	$(CXX) -shared -fPIC -pthread -o $@ $^
