@@ -470,6 +470,67 @@ int mvo_optimize_pose(mvo_ctx* ctx, const float* pts3d /* n x 3, world */, const
  * round run (inliers going in, chi2 at the start, chi2 at the end, trials, accepted steps, inliers coming out); *n_rounds is
  * set; MVO_ERR_CAPACITY if cap < *n_rounds, MVO_ERR_STATE before the first such call. */
 int mvo_debug_get_pose_optimize(mvo_ctx* ctx, double* rows /* cap x 6 */, int cap, int* n_rounds);
+/* ---- tracking the local map ------------------------------------------------------------------- */
+/* The reference's per-frame step ends with the pose (vo.cpp:267-347); ORB-SLAM's Tracking::TrackLocalMap goes on: with the
+ * optimised pose it projects every local map point the first search left unmatched (SearchLocalPoints, Frame::isInFrustum,
+ * ORBmatcher::SearchByProjection(F, vpMapPoints, th)) and optimises the pose again over the union.  This is that second
+ * search, declared operation by operation in DESIGN.md section 22, f64, every operation one IEEE operation in the written
+ * order, nothing from libm but sqrt.  Per map point i:
+ *   projection, in_view   the arithmetic of mvo_map_points_in_view, bit for bit (T_c_w by mvo_invert_pose)
+ *   dist      d_r = (double)pos_r - T_w_c[4 r + 3];  s = d_x d_x; s = s + d_y d_y; s = s + d_z d_z;  dist = sqrt(s)
+ *   in_range  md = (double)max_dist[i];  md > 0 && dist >= 0.8 * (md / level_scale[L-1]) && dist <= 1.2 * md
+ *   vc        ((d_x n_x + d_y n_y) + d_z n_z) / dist, n the f32 normal widened;  facing = vc >= min_view_cos (a NaN fails)
+ *   lv        the number of l in 0..L-2 with dist * level_scale[l] < md
+ *   r2        r r, r = (((vc > near_cos) ? radius_near : radius_far) * radius_scale) * level_scale[lv]
+ *   active    in_view && in_range && facing && !skip[i]
+ * Per pair: du, dv, d2 as in tracking by projection; pass = active && d2 <= r2 && (t_level[j] == lv || t_level[j] == lv - 1).
+ * The gate is inclusive.  One launch (k_map_match_local) per call; positions, descriptors and view data never leave HBM. */
+typedef struct {
+    double min_view_cos;  /* finite; default 0.5 (Frame::isInFrustum: viewCos < viewingCosLimit rejects) */
+    double radius_near;   /* >= 0, finite; default 2.5 (ORBmatcher::RadiusByViewingCos) */
+    double radius_far;    /* >= 0, finite; default 4.0 */
+    double near_cos;      /* finite; default 0.998 */
+    double radius_scale;  /* >= 0, finite; default 1.0 (the th of SearchByProjection) */
+    double lowe_ratio;    /* the filter of mvo_map_match_features_local; default 0.8 */
+    int32_t max_hamming;  /* ... default 100 (ORBmatcher::TH_HIGH) */
+    int32_t pad;
+} mvo_local_map_params;   /* NULL = defaults */
+/* MapPoint::GetNormal / MapPoint::GetMaxDistanceInvariance of the resident copy: normal n x 3 f32, max_dist n f32, n =
+ * mvo_map_size.  Stored as they come (a non-finite normal fails the facing test, max_dist <= 0 the range test).
+ * mvo_map_upload invalidates them: the calls below return MVO_ERR_INVALID until they are given again. */
+int mvo_map_upload_view(mvo_ctx* ctx, mvo_map* map, const float* normal /* n x 3 */, const float* max_dist /* n */);
+/* Tracking::SearchLocalPoints (Frame::isInFrustum + ORBmatcher::SearchByProjection(F, vpMapPoints, th)).  Raw: one row per
+ * map point.  Active: px = its pixel, idx / dist = the two nearest passing keypoints in 256-bit Hamming space with the tie rule
+ * and the missing-neighbour convention of mvo_match_knn2, n_candidates = the number of passing keypoints, level = lv, view_cos =
+ * vc.  Not active: px (0, 0), idx (-1, -1), dist (INT32_MAX, INT32_MAX), n_candidates -1, level -1, view_cos 0.0.
+ * t_level[j]: the octave of keypoint j in 0..n_levels-1, or -2 for a keypoint that is already connected and never passes.
+ * skip (n_map uint8 or NULL): nonzero for a point already matched in this frame.  level_scale: n_levels (1..16) positive,
+ * finite, strictly increasing.  px, n_candidates, level and view_cos are optional.
+ * MVO_ERR_INVALID: a null pointer with a positive count, a null map, no view data since the last upload, a singular or
+ * non-finite pose, fx or fy 0, cols or rows <= 0, a bad level_scale, a t_level entry outside its set, a parameter outside its
+ * range.  MVO_ERR_CAPACITY: nt > 65535.  Every check comes before the upload and nothing is written on error.  An empty map
+ * succeeds and writes nothing; nt == 0 succeeds (active points: n_candidates 0). */
+int mvo_map_match_knn2_local(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy,
+                             int cols, int rows, const uint8_t* t, const float* txy, const int32_t* t_level, int nt,
+                             const uint8_t* skip /* n_map or NULL */, const double* level_scale, int n_levels,
+                             const mvo_local_map_params* params, float* px, int32_t* idx, int32_t* dist,
+                             int32_t* n_candidates, int32_t* level, double* view_cos);
+/* Tracking::SearchLocalPoints.  The same with the frame's descriptors already in HBM; the other arrays stay host pointers. */
+int mvo_map_match_knn2_local_dev(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy,
+                                 int cols, int rows, const void* d_t, const float* txy, const int32_t* t_level, int nt,
+                                 const uint8_t* skip, const double* level_scale, int n_levels,
+                                 const mvo_local_map_params* params, float* px, int32_t* idx, int32_t* dist,
+                                 int32_t* n_candidates, int32_t* level, double* view_cos);
+/* ORBmatcher::SearchByProjection(F, vpMapPoints, th), its acceptance rule: the raw call, then point i is kept if idx0 >= 0,
+ * d0 <= max_hamming and (idx1 < 0 or t_level[idx0] != t_level[idx1] or (double)d0 <= lowe_ratio * (double)d1) -- the ratio
+ * counts only between neighbours of one level, and it is inclusive; one point per keypoint survives (smallest distance, then
+ * the lower map index); out is sorted by trainIdx, imgIdx 0, distance (float)d0, queryIdx the MAP index.  px (n_map x 2) and
+ * level (n_map) are optional.  MVO_ERR_CAPACITY (with *n set) if cap is too small. */
+int mvo_map_match_features_local(mvo_ctx* ctx, mvo_map* map, const double* T_w_c, double fx, double fy, double cx, double cy,
+                                 int cols, int rows, const uint8_t* t, const float* txy, const int32_t* t_level, int nt,
+                                 const uint8_t* skip, const double* level_scale, int n_levels,
+                                 const mvo_local_map_params* params, float* px, int32_t* level, mvo_dmatch* out, int cap,
+                                 int* n);
 /* ---- map points refreshed from their observations --------------------------------------------- */
 /* The reference gives a map point the descriptor and the viewing direction of the ONE frame that created it
  * (pushCurrPointsToMap_, vo.cpp:528-576) and never writes them again; ORB-SLAM, whose matching the calls above follow, keeps a

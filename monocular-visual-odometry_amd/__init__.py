@@ -114,6 +114,16 @@ class PoseOptimizeParams(C.Structure):
                 ("huber_delta", C.c_double), ("rel_tolerance", C.c_double)]
 
 
+class LocalMapParams(C.Structure):
+    """mvo_local_map_params (include/mvo_hip.h)."""
+    _fields_ = [("min_view_cos", C.c_double), ("radius_near", C.c_double), ("radius_far", C.c_double), ("near_cos", C.c_double),
+                ("radius_scale", C.c_double), ("lowe_ratio", C.c_double), ("max_hamming", C.c_int32), ("pad", C.c_int32)]
+
+
+LOCAL_MAP_DEFAULTS = dict(min_view_cos=0.5, radius_near=2.5, radius_far=4.0, near_cos=0.998, radius_scale=1.0, lowe_ratio=0.8,
+                          max_hamming=100)
+
+
 class InitPoses(C.Structure):
     """mvo_init_poses (include/mvo_hip.h)."""
     _fields_ = [("inliers_e", C.c_void_p), ("inliers_h", C.c_void_p), ("cap_inliers", C.c_int), ("pts3d", C.c_void_p),
@@ -506,6 +516,74 @@ class Context:
                                                              len(t), C.c_double(max_px), C.c_double(lowe_ratio), int(max_hamming),
                                                              _p(px), _p(in_view), _p(out), cap, C.byref(cnt)))
         return out[:cnt.value].copy(), px, in_view.astype(bool)
+
+    # ---- tracking the local map (ORB-SLAM's Tracking::SearchLocalPoints)
+    def map_upload_view(self, m, normal, max_dist):
+        """mvo_map_upload_view: the mean normals (n x 3 f32) and largest distances (n f32) of the resident map points."""
+        n = self._map_size(m)
+        normal = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        max_dist = np.ascontiguousarray(max_dist, np.float32).reshape(-1)
+        if len(normal) != n or len(max_dist) != n:
+            raise ValueError("one normal and one max_dist per resident map point")
+        self._chk(self.lib.mvo_map_upload_view(self.h, m, _p(normal), _p(max_dist)))
+
+    def _local_args(self, m, T_w_c, K, txy, t_level, skip, level_scale, params):
+        if not hasattr(self.lib, "mvo_map_match_knn2_local"):
+            raise MvoError(MVO_ERR_STATE, "this libmvo_hip.so has no mvo_map_match_knn2_local")
+        T, k, txy, _ = self._projection_args(T_w_c, K, txy, None)
+        t_level = np.ascontiguousarray(t_level, np.int32).reshape(-1)
+        if len(t_level) != len(txy):
+            raise ValueError("one level per frame keypoint")
+        n = self._map_size(m)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, np.uint8).reshape(-1)
+            if len(skip) != n:
+                raise ValueError("one skip flag per resident map point")
+        ls = np.ascontiguousarray(level_scale, np.float64).reshape(-1)
+        pp = None
+        if params:
+            v = dict(LOCAL_MAP_DEFAULTS, **params)
+            pp = C.byref(LocalMapParams(float(v["min_view_cos"]), float(v["radius_near"]), float(v["radius_far"]), float(v["near_cos"]),
+                                        float(v["radius_scale"]), float(v["lowe_ratio"]), int(v["max_hamming"]), 0))
+        return n, T, k, txy, t_level, skip, ls, pp
+
+    def _local_raw(self, fn, m, T_w_c, K, cols, rows, t, txy, t_level, level_scale, skip, params):
+        n, T, k, txy, t_level, skip, ls, pp = self._local_args(m, T_w_c, K, txy, t_level, skip, level_scale, params)
+        px, idx, dist = np.zeros((n, 2), np.float32), np.zeros((n, 2), np.int32), np.zeros((n, 2), np.int32)
+        cnt, lv, vc = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.float64)
+        self._chk(fn(self.h, m, _p(T), *k, int(cols), int(rows), t, _p(txy), _p(t_level), len(txy), _p(skip), _p(ls), len(ls), pp,
+                     _p(px), _p(idx), _p(dist), _p(cnt), _p(lv), _p(vc)))
+        return px, idx, dist, cnt, lv, vc
+
+    def map_match_knn2_local(self, m, T_w_c, K, cols, rows, t, txy, t_level, level_scale, skip=None, params=None):
+        """mvo_map_match_knn2_local: per map point that faces the camera within its range under T_w_c, its pixel and the two
+        nearest frame keypoints of its predicted level (or the one below) within its radius -> (px n_map x 2 f32, idx n_map x 2,
+        dist n_map x 2, n_candidates n_map, level n_map, view_cos n_map f64; n_candidates -1: not active).  t_level: the octave
+        per keypoint or -2 (taken); skip: n_map flags or None; params: a dict over LOCAL_MAP_DEFAULTS or None."""
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        if len(t) != len(np.asarray(txy).reshape(-1, 2)):
+            raise ValueError("one keypoint position per descriptor")
+        return self._local_raw(self.lib.mvo_map_match_knn2_local, m, T_w_c, K, cols, rows, _p(t), txy, t_level, level_scale, skip, params)
+
+    def map_match_knn2_local_dev(self, m, T_w_c, K, cols, rows, d_t, txy, t_level, level_scale, skip=None, params=None):
+        """The same with the frame's descriptors in HBM (a device pointer); the count comes from txy."""
+        return self._local_raw(self.lib.mvo_map_match_knn2_local_dev, m, T_w_c, K, cols, rows, C.c_void_p(d_t), txy, t_level,
+                               level_scale, skip, params)
+
+    def map_match_features_local(self, m, T_w_c, K, cols, rows, t, txy, t_level, level_scale, skip=None, params=None, cap=None):
+        """mvo_map_match_features_local: the raw call, ORB-SLAM's acceptance rule, one map point per keypoint ->
+        (DMATCH_DTYPE sorted by trainIdx with queryIdx = map index, px n_map x 2, level n_map)."""
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        n, T, k, txy, t_level, skip, ls, pp = self._local_args(m, T_w_c, K, txy, t_level, skip, level_scale, params)
+        if len(txy) != len(t):
+            raise ValueError("one keypoint position per descriptor")
+        cap = min(n, len(t)) if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), DMATCH_DTYPE)
+        px, lv = np.zeros((n, 2), np.float32), np.zeros(n, np.int32)
+        cnt = C.c_int()
+        self._chk(self.lib.mvo_map_match_features_local(self.h, m, _p(T), *k, int(cols), int(rows), _p(t), _p(txy), _p(t_level), len(t),
+                                                        _p(skip), _p(ls), len(ls), pp, _p(px), _p(lv), _p(out), cap, C.byref(cnt)))
+        return out[:cnt.value].copy(), px, lv
 
     def map_refresh(self, m, obs_desc, obs_cam, obs_start):
         """mvo_map_refresh: every map point takes the medoid of its observations' descriptors (in HBM) and the mean of their

@@ -183,7 +183,7 @@ void mvo_destroy(mvo_ctx* ctx) {
     track_release(ctx);
     // (the per-feature states free their device buffers on the current device: here, not in ~mvo_ctx)
     ctx->undist.reset(), ctx->epi.reset(), ctx->proj.reset(), ctx->dist.reset(), ctx->refresh.reset(), ctx->refine.reset();
-    ctx->fuse.reset(), ctx->window.reset(), ctx->pose_opt.reset();
+    ctx->fuse.reset(), ctx->window.reset(), ctx->pose_opt.reset(), ctx->local_map.reset();
     ba_pool_release(ctx);
     ctx->d_img.release(), ctx->d_mq.release(), ctx->d_mt.release(), ctx->d_mqxy.release(), ctx->d_mtxy.release(), ctx->d_mout.release();
     void* dev[] = {ctx->d_raw, ctx->d_blur, ctx->d_tabs, ctx->d_pyr_regs, ctx->d_kp, ctx->d_desc_buf, ctx->d_fh_slots, ctx->d_fh_line, ctx->d_fh_arrive};

@@ -219,6 +219,9 @@ struct mvo_map {  // the resident map (mvo_map_*, track_host.cpp): n x 3 f32 pos
     DevBuf<float> d_pos;
     DevBuf<uint8_t> d_desc;
     int n = 0;
+    // the view data of the points (mvo_map_upload_view, local_map_host.cpp): n x 3 f32 mean normals, n f32 largest distances
+    DevBuf<float> d_normal, d_max_dist;
+    bool has_view = false;  // given since the last mvo_map_upload
 };
 
 // undistortion (undistort_kernels.hip / undistort_host.cpp)
@@ -406,6 +409,20 @@ struct mvo_pose_opt_state {  // mvo_ctx::pose_opt, used by pose_optimize_host.cp
     double rows[PO_MAX_ROUNDS * 6] = {0};
 };
 
+// the local map tracked from the optimised pose (local_map_kernels.hip / local_map_host.cpp)
+#define LM_MAX_LEVELS 16
+struct LocalMapArgs {  // k_map_match_local: everything but the arrays travels in the kernel arguments
+    TrackViewArgs view;
+    double O[3];                         // the camera centre, T_w_c[4 r + 3]
+    double level_scale[LM_MAX_LEVELS];   // entries behind n_levels repeat the last one
+    double min_view_cos, radius_near, radius_far, near_cos, radius_scale;
+    int32_t n_levels, pad;
+};
+struct mvo_local_map_state {  // mvo_ctx::local_map, used by local_map_host.cpp
+    DevBuf<uint8_t> d_in;  // one upload per call: the parked keypoints, the skip mask, the descriptors of the host-pointer form
+    GuidedScratch scratch;
+};
+
 struct ProfEntry {
     int64_t launches = 0;
     double ms = 0;
@@ -479,7 +496,7 @@ struct mvo_ctx {
     // --- per-feature state, each made by the first call of its feature (mvo_state) and reset by mvo_destroy: undistortion,
     // pose-guided matching, tracking by projection, cell-wise FAST + quadtree spread, map points refreshed from / refined over
     // their observations, duplicate map points fused, new map points triangulated against the buffered frames, the pose from
-    // a robust motion-only optimisation
+    // a robust motion-only optimisation, the local map tracked from the optimised pose
     std::unique_ptr<mvo_undistort_state> undist;
     std::unique_ptr<mvo_epipolar_state> epi;
     std::unique_ptr<mvo_projection_state> proj;
@@ -489,6 +506,7 @@ struct mvo_ctx {
     std::unique_ptr<mvo_fuse_state> fuse;
     std::unique_ptr<mvo_window_state> window;
     std::unique_ptr<mvo_pose_opt_state> pose_opt;
+    std::unique_ptr<mvo_local_map_state> local_map;
     // --- BA diagnostics of the last fetched solve
     long long ba_phase[16] = {0};
     int ba_wgs = 0, ba_trials = 0;
@@ -626,6 +644,10 @@ int window_launch_verify(mvo_ctx* ctx, const WindowPairIn* d_pairs, int n, const
 // pose_optimize_kernels.hip
 int pose_optimize_launch(mvo_ctx* ctx, const float* d_p3, const float* d_p2, const float* d_s, int n, const PoseOptArgs& a, PoseOptOut* out,
                          uint8_t* out_outlier);
+// local_map_kernels.hip
+int local_map_launch(mvo_ctx* ctx, const float* d_pos, const uint8_t* d_desc, const float* d_normal, const float* d_max_dist, int n_map,
+                     const LocalMapArgs& a, const uint8_t* d_t, const double* d_tg, const uint8_t* d_skip, int nt, GuidedPartials part,
+                     int32_t* out);
 extern int g_pyr_force_chain;  // test hook (orb_kernels.hip)
 extern int g_match_mfma;       // test hook (match_kernels.hip)
 extern int g_pnp_replay_skew;  // test hook: the device replays the RANSAC loop with a wrong confidence

@@ -447,6 +447,7 @@ int mvo_map_upload(mvo_ctx* ctx, mvo_map* map, const float* pos, const uint8_t* 
     if (n_pos > map->d_pos.cap || n_desc > map->d_desc.cap) MVO_HIP(hipStreamSynchronize(ctx->stream));
     if ((r = map->d_pos.ensure(ctx, n_pos, 4096 * 3)) || (r = map->d_desc.ensure(ctx, n_desc, 4096 * 32))) return r;
     map->n = n;
+    map->has_view = false;  // (mvo_map_upload_view: the view data belong to the arrays they were given for)
     if (n) {
         // staged through pinned memory so that the caller's arrays may be reused as soon as we return
         if ((r = mvo_ensure_pinned(ctx, (size_t)n * 44))) return r;

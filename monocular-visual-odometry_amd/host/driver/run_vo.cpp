@@ -51,6 +51,20 @@
 // chi2_threshold, huber_delta, rel_tolerance (f64), OINI = the initial pose (16 f64), OP3D / OP2D / OSIG = the matches' map
 // points (n x 3 f32), pixels (n x 2 f32) and inv_sigma2 (n f32), OTWC / OTCW = the result (16 f64 each), OINF = info (6 int32),
 // OCHI = chi2 (2 f64), OOUT = the outlier flags (n); and always OFBK = int32, 1 if the frame fell back.
+// Optional key `tracking_local_map` (0 / 1, default 0; requires `tracking_pose_by_optimization: 1`, run_vo ends with an error that
+// says so otherwise): 1 makes every tracked frame whose pose came from the optimisation search the map a second time from that
+// pose -- the points the first search left unmatched that face the camera within their range of distances, against the free
+// keypoints of their predicted pyramid level or the one below within 2.5 to 4 px at that level (my_slam/vo/local_map.h; ORB-SLAM's
+// Tracking::TrackLocalMap) -- and optimise the pose again over the union.  Optional keys
+// `local_map_min_view_cos` (default 0.5), `local_map_radius_near` (2.5), `local_map_radius_far` (4.0), `local_map_radius_scale`
+// (1.0), `local_map_lowe_ratio` (0.8), `local_map_max_hamming` (100).  With the key on, a tracked frame's part of the frame log
+// carries after OFBK, if the pass was made: LSET = fx, fy, cx, cy, cols, rows, n_levels, min_view_cos, radius_near, radius_far,
+// near_cos, radius_scale, lowe_ratio, max_hamming, then the n_levels level scales (f64), LINI = the pose going in (16 f64), LSKP =
+// the skip mask (n), LLVL = the keypoints' levels (nt int32, -2: connected), LPOS / LDSC / LNRM / LMXD = the map as resident:
+// positions (n x 3 f32), descriptors (n x 32), normals (n x 3 f32), largest distances (n f32), LMAT = the new matches (queryIdx =
+// map row); if the second optimisation was called LP3D / LP2D / LSIG = its points, pixels and inv_sigma2 (f32), LTWC = its pose
+// (16 f64), LINF = info (6 int32), LCHI = chi2 (2 f64), LOUT = the outlier flags; and LAPP = int32 applied, int32 outcome (0: no new
+// matches, 1: more than 4096 observations, 2: not optimised, 3: moved too far from the previous frame, 4: applied).
 // Optional key `orb_distribute_keypoints` (0 / 1, default 0): 1 makes Frame::calcKeyPoints extract the ORB-SLAM way -- FAST cell by
 // cell with two thresholds, a quadtree spread per level (my_slam/geometry/orb_distribute.h; the reference's README.md section 5)
 // -- instead of cv::ORB::detect (feature_match.cpp:22-23).  Its four parameters, optional as well: `orb_distribute_ini_threshold`
@@ -129,6 +143,9 @@
 #pragma weak mvo_map_match_features_projection
 // ... or without the pose optimisation (`tracking_pose_by_optimization`): likewise
 #pragma weak mvo_optimize_pose
+// ... or without the second search of the local map (`tracking_local_map`): likewise
+#pragma weak mvo_map_upload_view
+#pragma weak mvo_map_match_features_local
 // ... or without the map-point refresh (`map_point_refresh`): likewise
 #pragma weak mvo_map_refresh
 // ... or without the position refinement (`map_point_refine_positions`): likewise
@@ -216,6 +233,28 @@ struct FrameLog {
                 vec("OOUT", fr->pose_opt_outlier_);
             }
             put("OFBK", &fr->pose_opt_fallback_, sizeof(int));
+        }
+        if (fr->local_map_applied_ >= 0) {  // `tracking_local_map: 1`: what the pass saw and gave, if it was made
+            vec("LSET", fr->local_map_setup_);
+            vec("LINI", fr->local_map_init_);
+            vec("LSKP", fr->local_map_skip_);
+            vec("LLVL", fr->local_map_t_level_);
+            vec("LPOS", fr->local_map_pos_);
+            vec("LDSC", fr->local_map_desc_);
+            vec("LNRM", fr->local_map_normal_);
+            vec("LMXD", fr->local_map_max_dist_);
+            vec("LMAT", fr->local_map_matches_);
+            if (!fr->local_map_info_.empty()) {
+                vec("LP3D", fr->local_map_p3_);
+                vec("LP2D", fr->local_map_p2_);
+                vec("LSIG", fr->local_map_sigma_);
+                vec("LTWC", fr->local_map_T_w_c_);
+                vec("LINF", fr->local_map_info_);
+                vec("LCHI", fr->local_map_chi2_);
+                vec("LOUT", fr->local_map_outlier_);
+            }
+            const int applied[2] = {fr->local_map_applied_, fr->local_map_outcome_};
+            put("LAPP", applied, sizeof applied);
         }
         vec("MMAP", fr->matches_with_map_);  // the PnP inliers' matches (vo.cpp:336-349)
         const int flags[2] = {good ? 1 : 0, is_keyframe ? 1 : 0};
@@ -428,6 +467,13 @@ int main(int argc, char** argv) {
                 throw std::runtime_error("tracking_pose_by_optimization requires tracking_match_by_projection: 1");
             if (!mvo_optimize_pose) throw std::runtime_error("tracking_pose_by_optimization: this libmvo_hip.so has no mvo_optimize_pose");
             printf("tracked frames take their pose from a robust optimisation over all matches\n");
+        }
+        if (vo::trackingLocalMap()) {
+            if (!vo::trackingPoseByOptimization())
+                throw std::runtime_error("tracking_local_map requires tracking_pose_by_optimization: 1");
+            if (!mvo_map_upload_view || !mvo_map_match_features_local)
+                throw std::runtime_error("tracking_local_map: this libmvo_hip.so has no mvo_map_match_features_local");
+            printf("tracked frames search the local map a second time from the optimised pose\n");
         }
         if (vo::mapPointRefresh()) {
             if (!mvo_map_refresh) throw std::runtime_error("map_point_refresh: this libmvo_hip.so has no mvo_map_refresh");

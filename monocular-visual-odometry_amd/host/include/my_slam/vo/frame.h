@@ -65,6 +65,18 @@ public:
     vector<float> pose_opt_p3_, pose_opt_p2_, pose_opt_sigma_;
     vector<int> pose_opt_info_;
     vector<unsigned char> pose_opt_outlier_;
+    // (not in the reference) `tracking_local_map: 1` (my_slam/vo/local_map.h): whether the second search was made (-1: not) and
+    // applied, its outcome (LocalMapOutcome) and what it saw and gave: the intrinsics, image size, number of levels, parameters
+    // and level scales; the optimised pose going in (16); the skip mask (n), the keypoints' levels (nt, -2: connected), the map
+    // as resident (n x 3 positions, n x 32 descriptors) with its view data (n x 3 normals, n largest distances); the new matches
+    // (queryIdx = map row); then, if the second optimisation was called, its points (k x 3), pixels (k x 2), inv_sigma2 (k), T_w_c
+    // (16), info (6), chi2 (2) and outlier flags (k); empty otherwise
+    int local_map_applied_ = -1, local_map_outcome_ = -1;
+    vector<double> local_map_setup_, local_map_init_, local_map_T_w_c_, local_map_chi2_;
+    vector<unsigned char> local_map_skip_, local_map_desc_, local_map_outlier_;
+    vector<int> local_map_t_level_, local_map_info_;
+    vector<float> local_map_pos_, local_map_normal_, local_map_max_dist_, local_map_p3_, local_map_p2_, local_map_sigma_;
+    vector<cv::DMatch> local_map_matches_;
     // (not in the reference) `map_point_refresh: 1`, on the keyframe after whose insertion the map points were refreshed
     // (my_slam/vo/map_refresh.h): the ids of MapOnDevice::order() as the frame's own tracking step saw it (the refresh re-reads
     // the map), then in the order of the refreshed map: the observation starts (n + 1), the observations' descriptors
@@ -164,6 +176,9 @@ public:
         inliers_matches_with_ref_.clear();
         inliers_matches_for_3d_.clear();
         matches_with_map_.clear();
+        local_map_skip_.clear(), local_map_desc_.clear(), local_map_pos_.clear();  // (logged by now; local_map_applied_ stays)
+        local_map_normal_.clear(), local_map_max_dist_.clear(), local_map_t_level_.clear(), local_map_matches_.clear();
+        local_map_p3_.clear(), local_map_p2_.clear(), local_map_sigma_.clear(), local_map_outlier_.clear();
         refresh_order_before_.clear();  // (logged by now; refreshed_ stays)
         refresh_obs_start_.clear();
         refresh_obs_desc_.clear();

@@ -21,6 +21,10 @@ public:
     cv::Mat descriptor_;           // 1 x 32
     bool good_ = true;
     int matched_times_ = 1, visible_times_ = 1;
+    // (not in the reference) ORB-SLAM's MapPoint::mfMaxDistance: the distance to the camera centre that created the point times
+    // the scale of the creating keypoint's octave -- the distance at which the point would appear on level 0; -1: not set
+    // (my_slam/vo/local_map.h rejects such a point)
+    float max_dist_ = -1;
 
     MapPoint(const cv::Point3f& pos, const cv::Mat& descriptor, const cv::Mat& norm, unsigned char r = 0,
              unsigned char g = 0, unsigned char b = 0)

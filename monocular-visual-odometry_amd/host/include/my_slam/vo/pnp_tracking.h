@@ -106,11 +106,32 @@ public:
             pos_[3 * i + 1] = order_[i]->pos_.y;
             pos_[3 * i + 2] = order_[i]->pos_.z;
         }
-        if (!same)
+        if (!same) {
             mvo_check(mvo_map_upload(hot_path_ctx(), map_, pos_.data(), desc_.data(), (int)n), "mvo_map_upload");
-        else
+            view_stale_ = true;  // (the upload invalidates the view data)
+        } else
             mvo_check(mvo_map_update_positions(hot_path_ctx(), map_, pos_.data(), 0, (int)n), "mvo_map_update_positions");
     }
+    // `tracking_local_map: 1` (my_slam/vo/local_map.h): sync(), then the view data of the points -- the mean normal as f32, the
+    // largest distance -- whenever the map was uploaded since, or a normal has been rewritten (my_slam/vo/map_refresh.h)
+    void syncView(const Map::Ptr& map) {
+        sync(map);
+        const size_t n = order_.size();
+        vector<float> normal(3 * n), max_dist(n);
+        for (size_t i = 0; i < n; ++i) {
+            for (int r = 0; r < 3; ++r) normal[3 * i + r] = (float)order_[i]->norm_.at<double>(r, 0);
+            max_dist[i] = order_[i]->max_dist_;
+        }
+        const bool same = !view_stale_ && normal.size() == normal_.size() &&
+                          (n == 0 || (std::memcmp(normal.data(), normal_.data(), n * 12) == 0 &&
+                                      std::memcmp(max_dist.data(), max_dist_.data(), n * 4) == 0));
+        if (same) return;
+        normal_.swap(normal), max_dist_.swap(max_dist);
+        mvo_check(mvo_map_upload_view(hot_path_ctx(), map_, normal_.data(), max_dist_.data()), "mvo_map_upload_view");
+        view_stale_ = false;
+    }
+    const vector<float>& normals() const { return normal_; }    // n x 3, as uploaded by the last syncView()
+    const vector<float>& maxDists() const { return max_dist_; }  // n
     mvo_map* handle() const { return map_; }
     const vector<MapPoint::Ptr>& order() const { return order_; }
     const unsigned char* descriptor(int i) const { return &desc_[32 * (size_t)i]; }
@@ -126,6 +147,8 @@ private:
     vector<MapPoint::Ptr> order_;
     vector<float> pos_;
     vector<unsigned char> desc_;
+    vector<float> normal_, max_dist_;
+    bool view_stale_ = true;
 };
 
 // VisualOdometry::getMappointsInCurrentView_ (vo.cpp:16-49).  Same three outputs (+ visible_times_++); the

@@ -59,6 +59,20 @@ inline bool mapPointCreateFromWindow() {  // the optional key, latched on first 
     return on;
 }
 
+// my_slam/vo/local_map.h (included at the end of window_triangulate.h): the second search of `tracking_local_map: 1`
+inline void trackLocalMap(TrackingState& st, const Frame::Ptr& curr, const cv::Mat& K);
+inline bool trackingLocalMap() {  // the optional key, latched on first use
+    static const bool on = basics::Config::has("tracking_local_map") && basics::Config::get<int>("tracking_local_map") != 0;
+    return on;
+}
+
+inline double octaveScale(int octave) {  // scale_factor multiplied octave times in f64, as matchMapByProjection does
+    static const double scale_factor = basics::Config::get<double>("scale_factor");
+    double s = 1.0;
+    for (int o = 0; o < octave; ++o) s *= scale_factor;
+    return s;
+}
+
 inline cv::Point3f preTranslatePoint3f(const cv::Point3f& p, const cv::Mat& T) {  // opencv_funcs.cpp:67-78
     const double q[4] = {p.x, p.y, p.z, 1};
     double res[3] = {0, 0, 0};
@@ -105,6 +119,7 @@ inline void pushCurrPointsToMap(TrackingState& st, const Frame::Ptr& curr) {
             const vector<unsigned char> rgb = pt_idx < (int)curr->kpts_colors_.size() ? curr->kpts_colors_[pt_idx]
                                                                                        : vector<unsigned char>{0, 0, 0};
             MapPoint::Ptr map_point(new MapPoint(world_pos, desc, norm, rgb[0], rgb[1], rgb[2]));
+            if (trackingLocalMap()) map_point->max_dist_ = (float)(len * octaveScale(curr->keypoints_[pt_idx].octave));
             map_point_id = map_point->id_;
             st.map_->insertMapPoint(map_point);
         }
@@ -166,6 +181,11 @@ inline bool trackFrame(TrackingState& st, const Frame::Ptr& curr, const cv::Mat&
         curr->T_w_c_ = st.ref_->T_w_c_.clone();  // Initial estimation of the current pose
     }
     const bool is_pnp_good = poseEstimationPnP(st.dev_map_, st.map_, curr, st.prev_, K);
+    if (trackingLocalMap()) {
+        if (!trackingPoseByOptimization()) throw std::runtime_error("tracking_local_map requires tracking_pose_by_optimization: 1");
+        // ORB-SLAM's TrackLocalMap: the map points the first search left unmatched, searched from the optimised pose
+        if (is_pnp_good && curr->pose_opt_fallback_ == 0) trackLocalMap(st, curr, K);
+    }
     if (is_pnp_good) {
         callBundleAdjustment(st.frames_buff_, st.map_, K);
         if (checkLargeMoveForAddKeyFrame(curr, st.ref_)) {

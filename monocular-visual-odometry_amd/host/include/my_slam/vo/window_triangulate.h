@@ -79,6 +79,7 @@ inline void createMapPointsFromWindow(TrackingState& st, const cv::Mat& K, const
         const vector<unsigned char> rgb = w.keypoint < (int)newest->kpts_colors_.size() ? newest->kpts_colors_[w.keypoint]
                                                                                       : vector<unsigned char>{0, 0, 0};
         MapPoint::Ptr map_point(new MapPoint(world_pos, desc, norm, rgb[0], rgb[1], rgb[2]));
+        if (trackingLocalMap()) map_point->max_dist_ = (float)(len * octaveScale(newest->keypoints_[w.keypoint].octave));
         st.map_->insertMapPoint(map_point);
         newest->inliers_to_mappt_connections_.insert({w.keypoint, PtConn{-1, map_point->id_}});
         st.frames_buff_[w.frame]->inliers_to_mappt_connections_.insert({w.train, PtConn{-1, map_point->id_}});
@@ -117,4 +118,6 @@ inline void createMapPointsFromWindow(TrackingState& st, const cv::Mat& K, const
 
 }  // namespace vo
 }  // namespace my_slam
+
+#include "my_slam/vo/local_map.h"  // (declared in tracking_loop.h)
 #endif
